@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Secret-scan throughput on MI355X (BASELINE.json metric, configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--gb G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--gb G] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 GPUs: under torchrun, one rank per GPU (rank r drives device LOCAL_RANK; WORLD_SIZE must
@@ -21,6 +21,11 @@ serialization of every per-file result.  Batches are pipelined across two device
 byte crosses PCIe in every step.  value = content bytes of all ranks x steps / max-over-
 ranks wall time of the timed steps.
 
+A plain run sets up, warms up, times the steps and prints the line; the CPU baselines and
+the sample check against the exact CPU path take runs of their own and are made only with
+--full (an --e2e run is a measurement of its own and always makes its check and stage
+breakdown).  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
+
 Rank 0 prints ONE JSON line with, besides the contract fields:
   roofline       K1 (the dominant kernel): algorithmic bytes per launch / mean HIP-event
                  duration of its launches (events on the lane stream around each launch)
@@ -31,14 +36,14 @@ Rank 0 prints ONE JSON line with, besides the contract fields:
                  (tools/fetch_calib.hip)
   kernels        K1, K2 (on the bytes it reads) and K1+gates+K2 GB/s (HIP events)
   pipeline       H2D GB/s, per-batch stage times, resolution time
-  cpu_baseline   the library's exact C++ CPU path (the reference algorithm restated:
+  cpu_baseline   (--full) the library's exact C++ CPU path (the reference algorithm restated:
                  per-rule keyword gate on bytes.ToLower, Go-semantics regexp over whole
                  files) on this host's cores, on a bounded sample of the same corpus
-  cpu_optimised  the GPU algorithm (K1 automaton + K2 DFAs + the same exact resolution)
+  cpu_optimised  (--full) the GPU algorithm (K1 automaton + K2 DFAs + the same exact resolution)
                  emulated on the same cores and sample
   checks         every step's findings (files with findings, findings) must equal the
-                 warmup step's, and a device scan of the cpu_baseline sample must be
-                 byte-identical to the exact CPU path's result; the bench fails otherwise
+                 warmup step's, and with --full a device scan of the cpu_baseline sample must
+                 be byte-identical to the exact CPU path's result; the bench fails otherwise
 """
 import argparse
 import json
@@ -242,6 +247,56 @@ def rule_set(name):
             "BASELINE configs[4] shape)", len(sc.Rules))
 
 
+DUMP_CAP_BYTES = {"result_bytes": 40 << 20, "file_status": 8 << 20, "findings": 8 << 20}  # < 64 MB in all
+
+
+def result_arrays(bufs):
+    """The results a caller of the timed path receives (tsg_result buffers, in submission
+    order) as arrays: every byte of the buffers, each file's status, and one row per finding
+    (file index over all buffers, rule index, start line, end line, match length)."""
+    import struct
+    import numpy as np
+    status, rows, base = [], [], 0
+    for buf in bufs:
+        magic, nfiles = struct.unpack_from("<II", buf, 0)
+        assert magic == 0x31475354
+        st = np.empty(nfiles, dtype=np.float32)
+        pos = 8
+        for i in range(nfiles):
+            st[i] = buf[pos]
+            (nf,) = struct.unpack_from("<I", buf, pos + 1)
+            pos += 5
+            for _ in range(nf):
+                ri, sl, el, ml = struct.unpack_from("<IiiI", buf, pos)
+                pos += 16 + ml
+                (nl,) = struct.unpack_from("<I", buf, pos)
+                pos += 4
+                for _ in range(nl):
+                    (cl,) = struct.unpack_from("<I", buf, pos + 5)
+                    pos += 9 + cl
+                rows.append((base + i, ri, sl, el, ml))
+        assert pos == len(buf)
+        status.append(st)
+        base += nfiles
+    raw = np.frombuffer(b"".join(bufs), dtype=np.uint8).astype(np.float32)
+    return {"result_bytes": raw,
+            "file_status": np.concatenate(status) if status else np.zeros(0, np.float32),
+            "findings": np.array(rows, dtype=np.float64).reshape(-1, 5)}
+
+
+def dump_outputs(dirname, bufs, suffix=""):
+    """Write the last timed step's results as DIR/<name>.npy (float32 / float64).  An array
+    over its cap is cut to a fixed, seeded sample of its rows (in order), so two builds run
+    with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in result_arrays(bufs).items():
+        cap = DUMP_CAP_BYTES[name] // max(1, a.itemsize * (a.shape[1] if a.ndim > 1 else 1))
+        if len(a) > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=cap, replace=False))]
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
+
+
 def fill_slots(ctx, batch, batch_bytes):
     """Pack the corpus into pinned slots of about batch_bytes each (outside timing)."""
     import numpy as np
@@ -281,10 +336,13 @@ class DeviceRun:
     def __init__(self, ctx, slots, info, depth, log):
         self.ctx, self.slots, self.info, self.depth, self.log = ctx, slots, info, depth, log
         self.step_findings = []  # (files with findings, findings) of every step, warmup included
+        self.kept = []  # result handles of the last step of a run(keep_last=True), unfreed
 
-    def run(self, steps, verbose=True):
+    def run(self, steps, verbose=True, keep_last=False):
         """`steps` scans of the share, pipelined across step boundaries (batches of step k+1
-        are submitted while step k's last ones resolve); every result is collected."""
+        are submitted while step k's last ones resolve); every result is collected.
+        keep_last: the last step's results stay in self.kept (in slot order) instead of
+        being freed."""
         import collections
         import ctypes as C
         from trivy_amd import _native as N
@@ -297,7 +355,10 @@ class DeviceRun:
             out = C.c_void_p()
             N.check(L.tsg_batch_collect(self.ctx.handle, t, C.byref(out)))
             ff, nf = _summary(out)
-            L.tsg_result_free(out)
+            if keep_last and k == steps - 1:
+                self.kept.append(out)
+            else:
+                L.tsg_result_free(out)
             per_step[k][0] += ff
             per_step[k][1] += nf
 
@@ -363,6 +424,11 @@ def main():
                     help="host resolution pool threads (0: library default, 16)")
     ap.add_argument("--cpu-mib", type=int, default=1024, help="CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baselines and the check of a "
+                         "device scan of their sample against the exact CPU path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --gb is the whole job's corpus, split over the GPUs "
                          "(each generates and scans its 1/N share); default: --gb per GPU")
@@ -462,16 +528,16 @@ def main():
     import ctypes as C
     import threading
 
-    def run_all(steps):
+    def run_all(steps, keep_last=False):
         """every device's share, one host thread per device (the native calls release the GIL)"""
         if len(runs) == 1:
-            runs[0].run(steps)
+            runs[0].run(steps, keep_last=keep_last)
             return
         errs = []
 
         def one(r, verbose):
             try:
-                r.run(steps, verbose)
+                r.run(steps, verbose, keep_last)
             except BaseException as e:  # noqa: BLE001 (re-raised below)
                 errs.append(e)
         th = [threading.Thread(target=one, args=(r, i == 0)) for i, r in enumerate(runs)]
@@ -486,7 +552,7 @@ def main():
     st0 = [r.ctx.stats() for r in runs]
     _barrier(dist)
     t0 = time.perf_counter()
-    run_all(args.steps)
+    run_all(args.steps, keep_last=bool(args.dump_outputs))
     _barrier(dist)
     dt = time.perf_counter() - t0
     st = [r.ctx.stats() for r in runs]
@@ -622,7 +688,10 @@ def main():
     line["checks"] = {"findings_per_step": sum(r.step_findings[0][1] for r in runs),
                       "files_with_findings_per_step": sum(r.step_findings[0][0] for r in runs),
                       "steps_checked": len(runs[0].step_findings)}
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.dump_outputs:  # devices in order, each one's batches in slot order
+        dump_outputs(args.dump_outputs, [_raw(out) for r in runs for out in r.kept],
+                     "" if world == 1 else "_rank%d" % rank)
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         nt = args.host_threads or cpu_share()[0]
         exact, opt, sub, exact_bytes = cpu_baselines(sc, batch0, args.cpu_mib << 20, nt)
         # (a one-GPU figure: reported at N=1; at N>1 the sample only checks the device)
@@ -722,10 +791,12 @@ def main_e2e(args):
     ctx = S.GpuContext(sc, 0, host_threads=args.host_threads, slot_mib=args.e2e_slot_mib, emulate=args.emulate)
     scanned = int(ref.batch.offsets[-1])
 
-    def step(check=False):
+    def step(check=False, keep=False):
         out = C.c_void_p()
         one_call(ctx, out)
         summ = _summary(out)
+        if keep:  # the caller reads and frees it
+            return summ, out
         return summ, (_raw(out) if check else L.tsg_result_free(out))
 
     for _ in range(max(1, args.warmup)):
@@ -737,11 +808,13 @@ def main_e2e(args):
     if raw0 != _raw(out):
         raise SystemExit("bench --e2e: device results differ from the exact CPU path")
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        summ, _ = step()
+    for k in range(args.steps):
+        summ, last_out = step(keep=bool(args.dump_outputs) and k == args.steps - 1)
         if summ != summ0:
             raise SystemExit("bench --e2e: findings differ between steps")
     dt = time.perf_counter() - t0
+    if args.dump_outputs and args.steps:
+        dump_outputs(args.dump_outputs, [_raw(last_out)])
     # stage breakdown, unpipelined: the whole input packed into one slot, then scanned
     a = time.perf_counter()
     g = unpiped(ctx)

@@ -27,7 +27,7 @@ def _line(r):
 
 
 def test_two_devices_one_process_emulated():
-    line = _line(_run(["--gpus", "2", "--emulate"] + SMALL))
+    line = _line(_run(["--gpus", "2", "--emulate", "--full"] + SMALL))
     assert line["n_gpus"] == 2
     assert line["config"]["devices"] == [0, 1]
     assert "tsg_multi" in line["config"]["parallelism"]
@@ -40,6 +40,30 @@ def test_two_devices_one_process_emulated():
     assert one["n_gpus"] == 1
     # device 0's share is the same corpus in both runs (seeded by the GPU index)
     assert one["config"]["bytes_per_gpu"] == line["config"]["bytes_per_gpu"]
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the contract fields and no CPU baseline or sample check;
+    --dump-outputs writes the last timed step's results, the same from run to run."""
+    import numpy as np
+    lines, dumps = [], []
+    for d in ("a", "b"):
+        lines.append(_line(_run(["--gpus", "1", "--emulate", "--dump-outputs", str(tmp_path / d)] + SMALL)))
+        dumps.append({n: np.load(str(tmp_path / d / (n + ".npy")))
+                      for n in ("result_bytes", "file_status", "findings")})
+    line = lines[0]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert "cpu_baseline" not in line and "cpu_optimised" not in line
+    assert "sample_device_eq_exact_cpu" not in line["checks"]
+    assert line["checks"]["steps_checked"] == 3
+    a, b = dumps
+    assert a["result_bytes"].dtype == np.float32 and a["findings"].dtype == np.float64
+    assert len(a["file_status"]) == line["config"]["files_per_gpu"]
+    assert a["findings"].shape == (line["checks"]["findings_per_step"], 5) and len(a["findings"]) > 0
+    assert int((a["file_status"] == 2).sum()) == line["checks"]["files_with_findings_per_step"]
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 def test_more_gpus_than_visible_fails():
@@ -89,7 +113,7 @@ def test_eight_devices_one_process_emulated():
     emulated devices; image.go:210-234's per-layer goroutines and gather): every device gets
     its share, its own slots and lanes at the run's depth, and the resolver pool sized for
     eight devices; the sample check and the per-step findings check pass."""
-    line = _line(_run(["--gpus", "8", "--emulate", "--gb", "0.004", "--batch-mib", "1", "--steps", "2",
+    line = _line(_run(["--gpus", "8", "--emulate", "--full", "--gb", "0.004", "--batch-mib", "1", "--steps", "2",
                        "--warmup", "1", "--depth", "4", "--cpu-mib", "1"], timeout=600))
     assert line["n_gpus"] == 8
     assert line["config"]["devices"] == list(range(8))

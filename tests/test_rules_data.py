@@ -9,17 +9,25 @@ the table uses: string literals, the pattern constants, `MustCompile(x)` and
 compared, so a transcription error in any of the 83 rules fails here, not only in the
 dozen rules the reference fixtures exercise.
 
-Reads /root/reference as text (it is absent on the GPU box: skipped there)."""
+The Go source is not part of this repository.  What that parse found is recorded in
+tests/golden/builtin_rules_go_digest.json: per rule and allow rule, in table order, its ID
+and the sha256 of its canonical field record (every field of the table, absent ones with
+Go's zero value).  The tests compare the product's rule data with that record, so they
+need nothing outside the tree.  Where a checkout of the reference is at hand,
+
+    TSG_REFERENCE_SRC=<reference>/pkg/fanal/secret python -m pytest tests/test_rules_data.py
+
+also re-parses the Go source, compares it field by field as well, and checks that the
+record is that parse's; `python -m tests.test_rules_data --record` rewrites the record from
+it."""
+import hashlib
 import json
 import os
 
-import pytest
-
-REF = "/root/reference/pkg/fanal/secret"
-RULES_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                          "trivy_amd", "rules", "builtin_rules.json")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference source not present")
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.environ.get("TSG_REFERENCE_SRC", "")
+RULES_JSON = os.path.join(os.path.dirname(HERE), "trivy_amd", "rules", "builtin_rules.json")
+DIGESTS = os.path.join(HERE, "golden", "builtin_rules_go_digest.json")
 
 
 def tokenize(src):
@@ -165,33 +173,72 @@ def consts_of(toks):
     return consts
 
 
-def test_builtin_rules_match_go_source():
+RULE_KEYS = ("id", "category", "title", "severity", "regex", "secret_group_name", "keywords")
+ALLOW_KEYS = ("id", "description", "regex", "path")
+
+
+def digest(record):
+    return hashlib.sha256(json.dumps(record, sort_keys=True, ensure_ascii=True).encode()).hexdigest()
+
+
+def go_rules():
+    """The rule table of the Go source as canonical field records."""
     src = open(os.path.join(REF, "builtin-rules.go")).read()
     toks = tokenize(src)
     consts = consts_of(toks)
     rules = Walker(toks, consts).slice_of_structs("builtinRules")
-    mine = json.load(open(RULES_JSON))
-    assert len(rules) == len(mine["rules"]) == 83
-    for go, j in zip(rules, mine["rules"]):
-        assert j["id"] == go["ID"]
-        assert j["category"] == go["Category"], go["ID"]
-        assert j["title"] == go["Title"], go["ID"]
-        assert j["severity"] == go.get("Severity", ""), go["ID"]
-        assert j["regex"] == go["Regex"], go["ID"]
-        assert j["secret_group_name"] == go.get("SecretGroupName", ""), go["ID"]
-        assert j["keywords"] == go.get("Keywords", []), go["ID"]
+    for go in rules:
         assert set(go) <= {"ID", "Category", "Title", "Severity", "Regex", "SecretGroupName",
                            "Keywords"}, go["ID"]
+    return [{"id": go["ID"], "category": go["Category"], "title": go["Title"],
+             "severity": go.get("Severity", ""), "regex": go["Regex"],
+             "secret_group_name": go.get("SecretGroupName", ""),
+             "keywords": go.get("Keywords", [])} for go in rules]
+
+
+def go_allow_rules():
+    src = open(os.path.join(REF, "builtin-allow-rules.go")).read()
+    allow = Walker(tokenize(src), {}).slice_of_structs("builtinAllowRules")
+    return [{"id": go["ID"], "description": go.get("Description", ""), "regex": go.get("Regex"),
+             "path": go.get("Path")} for go in allow]
+
+
+def _recorded(records):
+    return [{"id": r["id"], "sha256": digest(r)} for r in records]
+
+
+def _check(mine, keys, recorded, parse):
+    assert len(mine) == len(recorded)
+    for j, rec in zip(mine, recorded):
+        assert j["id"] == rec["id"]
+        assert digest({k: j[k] for k in keys}) == rec["sha256"], rec["id"]
+    if REF:  # a checkout of the reference: every field by name, and the record itself
+        go = parse()
+        assert _recorded(go) == recorded
+        for g, j in zip(go, mine):
+            for k in keys:
+                assert j[k] == g[k], (g["id"], k)
+
+
+def test_builtin_rules_match_go_source():
+    mine = json.load(open(RULES_JSON))["rules"]
+    recorded = json.load(open(DIGESTS))["rules"]
+    assert len(recorded) == 83
+    _check(mine, RULE_KEYS, recorded, go_rules)
 
 
 def test_builtin_allow_rules_match_go_source():
-    src = open(os.path.join(REF, "builtin-allow-rules.go")).read()
-    toks = tokenize(src)
-    allow = Walker(toks, {}).slice_of_structs("builtinAllowRules")
     mine = json.load(open(RULES_JSON))["allow_rules"]
-    assert len(allow) == len(mine)
-    for go, j in zip(allow, mine):
-        assert j["id"] == go["ID"]
-        assert j["description"] == go.get("Description", ""), go["ID"]
-        assert j["regex"] == go.get("Regex"), go["ID"]
-        assert j["path"] == go.get("Path"), go["ID"]
+    recorded = json.load(open(DIGESTS))["allow_rules"]
+    assert len(recorded) == 12
+    _check(mine, ALLOW_KEYS, recorded, go_allow_rules)
+
+
+if __name__ == "__main__":
+    import sys
+    if "--record" in sys.argv and REF:
+        with open(DIGESTS, "w") as f:
+            json.dump({"rules": _recorded(go_rules()), "allow_rules": _recorded(go_allow_rules())}, f, indent=1)
+            f.write("\n")
+    else:
+        raise SystemExit("usage: TSG_REFERENCE_SRC=<reference>/pkg/fanal/secret python -m tests.test_rules_data --record")

@@ -8,7 +8,7 @@ tag=${1:-r2}; shift
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-echo "== bench" && timeout -k 10 400 python -u bench.py "$@" > $out/bench.json 2> $out/bench.err || exit 1
+echo "== bench" && timeout -k 10 400 python -u bench.py --full "$@" > $out/bench.json 2> $out/bench.err || exit 1
 tail -c 3000 $out/bench.json
 echo "== kernel trace" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
   python bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > $out/trace.out 2>&1 || exit 2

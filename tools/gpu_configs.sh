@@ -10,8 +10,8 @@ echo "== tests" && timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --ti
 tail -3 $out/gpu_tests.log
 echo "== configs[0]" && timeout -k 10 400 python -u tools/fs_bench.py > $out/fs_bench.json 2> $out/fs_bench.err || { tail -20 $out/fs_bench.err; exit 2; }
 cat $out/fs_bench.json
-echo "== configs[3]" && timeout -k 10 500 python -u bench.py --rules user1000 --steps 2 --warmup 1 --cpu-mib 32 > $out/bench_user1000.json 2> $out/bench_user1000.err || { tail -20 $out/bench_user1000.err; exit 3; }
+echo "== configs[3]" && timeout -k 10 500 python -u bench.py --full --rules user1000 --steps 2 --warmup 1 --cpu-mib 32 > $out/bench_user1000.json 2> $out/bench_user1000.err || { tail -20 $out/bench_user1000.err; exit 3; }
 cat $out/bench_user1000.json
-echo "== configs[4]" && timeout -k 10 400 python -u bench.py --rules allow-exclude --steps 2 --warmup 1 --cpu-mib 256 > $out/bench_allow.json 2> $out/bench_allow.err || { tail -20 $out/bench_allow.err; exit 4; }
+echo "== configs[4]" && timeout -k 10 400 python -u bench.py --full --rules allow-exclude --steps 2 --warmup 1 --cpu-mib 256 > $out/bench_allow.json 2> $out/bench_allow.err || { tail -20 $out/bench_allow.err; exit 4; }
 cat $out/bench_allow.json
 echo done

@@ -9,7 +9,7 @@ echo "== tests" && timeout -k 10 700 python -u -m pytest tests -x -q -m gpu --ti
 tail -1 $out/gpu_tests.log
 echo "== smoke" && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 || { tail $out/smoke.log; exit 2; }
 tail -1 $out/smoke.log
-echo "== bench" && timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 3; }
+echo "== bench" && timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 3; }
 python -c "import json; d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['roofline']['frac'], d['roofline']['traffic'], d['kernels']['device_ms_per_batch'])"
 export TSG_LAYER_PROF=1
 for r in 1 2 3; do

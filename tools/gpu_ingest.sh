@@ -12,6 +12,6 @@ echo "== e2e fs" && timeout -k 10 300 python -u bench.py --e2e fs --steps 3 > $o
 cat $out/e2e_fs.json
 echo "== e2e layer" && timeout -k 10 400 python -u bench.py --e2e layer --steps 3 > $out/e2e_layer.json 2> $out/e2e_layer.err || { tail $out/e2e_layer.err; exit 3; }
 cat $out/e2e_layer.json
-echo "== configs[4]" && timeout -k 10 400 python -u bench.py --rules allow-exclude --steps 2 --warmup 1 --cpu-mib 256 > $out/bench_allow.json 2> $out/bench_allow.err || { tail $out/bench_allow.err; exit 4; }
+echo "== configs[4]" && timeout -k 10 400 python -u bench.py --full --rules allow-exclude --steps 2 --warmup 1 --cpu-mib 256 > $out/bench_allow.json 2> $out/bench_allow.err || { tail $out/bench_allow.err; exit 4; }
 cat $out/bench_allow.json
 echo done

@@ -12,6 +12,6 @@ echo "== smoke" && timeout -k 10 300 python -u -c "import __graft_entry__ as g; 
 tail -1 $out/smoke.log
 bash tools/gpu_bench_prof.sh ${1:-r04/close}/bench || exit 3
 bash tools/gpu_bench_prof.sh ${1:-r04/close}/u1000 --rules user1000 --cpu-mib 256 || exit 4
-echo "== bench allow-exclude" && timeout -k 10 400 python -u bench.py --rules allow-exclude > $out/bench_allow.json 2> $out/bench_allow.err || { tail $out/bench_allow.err; exit 5; }
+echo "== bench allow-exclude" && timeout -k 10 400 python -u bench.py --full --rules allow-exclude > $out/bench_allow.json 2> $out/bench_allow.err || { tail $out/bench_allow.err; exit 5; }
 head -c 400 $out/bench_allow.json; echo
 echo done

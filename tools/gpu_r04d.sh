@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 echo "== tests" && timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread \
   > $out/gpu_tests.log 2>&1 || { tail -30 $out/gpu_tests.log; exit 1; }
 tail -1 $out/gpu_tests.log
-echo "== bench" && timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 2; }
+echo "== bench" && timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 2; }
 python -c "
 import json; d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1]); k=d['kernels']
 print(d['value'], {x:k[x] for x in k if 'ms' in x and 'per_batch' in x})"

@@ -11,7 +11,7 @@ echo "== gpu suite" && timeout -k 10 900 python -u -m pytest -x -v --timeout 120
 tail -1 $out/tests.log
 echo "== smoke" && timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail $out/smoke.log; exit 2; }
 tail -3 $out/smoke.log
-echo "== bench" && timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 3; }
+echo "== bench" && timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 3; }
 python -c "import json; d=json.load(open('$out/bench.json')); r=d['roofline']; k=d['kernels']; print(d['value'], 'ev', r['frac_events'], 'clk', r['frac_clock'], r['k1_clock_ms_per_batch'], k['k1_ms_per_batch'], 'chain', r['chain_clock_ms_per_batch'], r['post_k1_clock_ms_per_batch'], r['device_frac'], d['cpu_baseline'])"
 echo "== traced bench" && timeout -k 10 -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
   python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_traced.json 2> $out/bench_traced.err || { tail $out/bench_traced.err; exit 4; }
