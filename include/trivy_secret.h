@@ -147,7 +147,9 @@ int tsg_result_summary(const tsg_result* r, uint64_t* nfiles, uint64_t* files_wi
 typedef struct tsg_ctx_options {
   uint32_t chunk_bytes;      /* bytes per lane (multiple of 16); 0 = default */
   uint32_t ext_cap;          /* max bytes a lane follows a match past its chunk; 0 = default */
-  uint32_t cand_capacity;    /* candidate records per batch; 0 = default */
+  uint32_t cand_capacity;    /* candidate records per batch (K2 drops the records past it and
+                                flags their files, which the host then resolves whole);
+                                0 = 4 Mi */
   int32_t host_threads;      /* resolver threads; <= 0 = 16 */
   uint32_t adapt_mib;        /* first batch of at least this many MiB samples K1's literal
                                 frequencies and stops reporting the frequent ones (their
@@ -217,6 +219,20 @@ int tsg_scan_batch(tsg_ctx* ctx, const uint8_t* data, const uint64_t* offsets, u
  * event bits [ceil(bytes / chunk_bytes)] (either pointer may be NULL). */
 int tsg_batch_kernels(tsg_ctx* ctx, uint32_t slot_id, uint32_t nfiles, uint32_t* kw,
                       size_t kw_len, uint32_t* ev, size_t ev_len);
+/* Test hook: K2's work lists as the item passes of the last tsg_batch_kernels left them on
+ * its lane (same slot, nothing submitted to the context in between: TSG_ERR_ARG otherwise;
+ * synchronous, like tsg_batch_kernels).  n[0..2] = list entries, dense entries and the item
+ * array in use on the device (tsg_stats.k2_items: a skipped list group keeps its region,
+ * which may lie past the array's end and is not copied); up to the given capacities are
+ * copied (any pointer may be NULL):
+ *   entries   4 u32 each: {group, first item, items (<= 512, one group), 1}
+ *   dentries  4 u32 each: {group, first chunk, chunks (<= 1,024), 2}
+ *   items     2 u32 each: (file, chunk); a list group's items lie at [first item, + items)
+ *             of its entries, in any order
+ *   gskip     [n_groups] 1 = the group was skipped (left to the host) */
+int tsg_batch_items(tsg_ctx* ctx, uint32_t slot_id, uint32_t* entries, size_t entries_cap,
+                    uint32_t* dentries, size_t dentries_cap, uint32_t* items, size_t items_cap,
+                    uint8_t* gskip, size_t gskip_len, uint64_t* n);
 
 typedef struct tsg_stats {
   double k1_ms;          /* K1 literal automaton + run counters, last collected batch (HIP events) */
@@ -228,9 +244,11 @@ typedef struct tsg_stats {
   uint64_t candidates;   /* candidate records produced */
   uint64_t files_resolved;  /* files with findings */
   uint32_t k2_launches;  /* K2 work-list entries */
-  uint32_t overflow;     /* 1 if the candidate buffer overflowed (files resolved whole) */
+  uint32_t overflow;     /* 1 if candidates > the context's cand_capacity (records dropped,
+                            their files resolved whole) */
   double gate_ms;        /* keyword gates + items + device-side layout */
-  uint64_t k2_items;     /* (file, chunk) items K2 scanned */
+  uint64_t k2_items;     /* (file, chunk) items of K2's list groups (the item array in use: a
+                            skipped list group's reserved region counts too) */
   uint32_t k1_hot_states;  /* K1 automaton states no longer reported (adaptation) */
   double h2d_ms;         /* H2D of the batch (pinned slot -> HBM) */
   uint32_t groups_skipped; /* rule groups K2 left to the host (item capacity) */
@@ -262,6 +280,11 @@ typedef struct tsg_stats {
   double k1_clock_ms, chain_clock_ms, post_k1_clock_ms;
   /* their sums over the batches collected so far */
   double sum_k1_clock_ms, sum_chain_clock_ms, sum_post_k1_clock_ms;
+  /* last batch: entries of K2's dense pass (1,024 consecutive chunks each, per dense group) */
+  uint32_t k2_dense_entries;
+  /* 1: K2's list pass runs k2_kernel_rich on this device, 0: k2_kernel (the occupancy API
+   * decides when the context is created) */
+  uint32_t k2_rich;
 } tsg_stats;
 int tsg_ctx_get_stats(const tsg_ctx* ctx, tsg_stats* out);
 
@@ -329,6 +352,13 @@ const char* tsg_last_error(void);
  *                     small test batches
  *   "k1f_list"        "1": K1F lists the chunks with events itself (no gates pass; the item
  *                     passes gate files from their keyword bits)
+ *   "k2_items_cap"    K2's item capacity in the next batches (default: twice the batch's
+ *                     chunks, at least 65,536); list groups past it are left to the host
+ *   "k2_max_dense"    1..16: rule groups the dense pass takes in the next batches (default
+ *                     16); further groups that want it are left to the host
+ *   "k2_no_word_recs" "1": K2 writes a record per accepting transition instead of one per
+ *                     accepting 16-B word, as for rule sets of 16,384 groups and more (the
+ *                     emulation then ignores emu_wordrec)
  * Returns TSG_ERR_ARG for an unknown name. */
 int tsg_test_knob(const char* name, const char* value);
 
@@ -357,6 +387,28 @@ int64_t tsg_regex_dfa_ends(const tsg_regex* re, const uint8_t* text, size_t len,
 int tsg_emulate_candidate_stats(const tsg_ruleset* rs, const uint8_t* data,
                                 const uint64_t* offsets, uint32_t nfiles, uint32_t chunk,
                                 uint64_t* cand_per_rule, uint64_t* gated_bytes_per_group);
+
+/* The item set K2 scans (plan.hpp emulate_items, which the emulation itself calls), from
+ * k1_reference's output: group g, file f, chunk c is an item iff g is gated for f (always,
+ * or one of its keywords' bits), c is a chunk of f (empty files have none) and a chunk in
+ * [c, min(c + back_g, last chunk of f)] carries one of g's event bits; a group with back_g >
+ * max_back listens to every chunk (16: the device's rule, 0xFFFFFFFF: the emulation's).
+ * triples (or NULL): up to triples_cap sorted (group, file, chunk); counts (or NULL)
+ * [n_groups]: items per group; *n_items (or NULL): all items. */
+int tsg_emulate_items(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
+                      uint32_t nfiles, uint32_t chunk, uint32_t max_back, uint32_t* triples,
+                      size_t triples_cap, uint64_t* counts, uint64_t* n_items);
+
+/* The device's item layout restated on the host (plan.hpp layout_reference), groups in id
+ * order: kind[g] = 0 no items, 1 list, 2 dense, 3 skipped.  A group with counts[g] * 2 >
+ * nchunks wants the dense pass and gets it while fewer than max_dense groups before it wanted
+ * it; any other group with items wants the region of the item array behind the regions of
+ * the list-wanting groups before it (a skipped group keeps its region) and is listed when the
+ * region ends within items_cap.  totals (or NULL) = {item array in use, list entries (512
+ * items), dense entries (1,024 chunks), skipped groups}: tsg_stats' k2_items, k2_launches,
+ * k2_dense_entries and groups_skipped. */
+int tsg_layout_reference(const uint64_t* counts, uint32_t n_groups, uint64_t nchunks,
+                         uint64_t items_cap, uint32_t max_dense, uint8_t* kind, uint64_t* totals);
 
 /* K1 reference semantics on the CPU (plan.hpp k1_reference): same layout as
  * tsg_batch_k1_output. */

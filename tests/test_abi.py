@@ -40,6 +40,21 @@ def test_ctypes_binding_covers_header():
     assert set(declared()) <= bound, set(declared()) - bound
 
 
+def test_stats_binding_follows_header():
+    """N.Stats lists tsg_stats' fields in the header's order, with k2_dense_entries and
+    k2_rich appended last (earlier fields keep their offsets)."""
+    src = open(HEADER).read()
+    body = re.search(r"typedef struct tsg_stats \{(.*?)\} tsg_stats;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    ctype = {"double": C.c_double, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
+    fields = []
+    for decl in body.split(";"):
+        words = decl.replace(",", " ").split()
+        fields += [(name, ctype[words[0]]) for name in words[1:]]
+    assert fields == list(N.Stats._fields_)
+    assert [n for n, _ in fields[-2:]] == ["k2_dense_entries", "k2_rich"]
+
+
 def test_config_error_and_last_error():
     h = C.c_void_p()
     err = C.create_string_buffer(256)

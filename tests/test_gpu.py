@@ -7,7 +7,7 @@ import os
 import pytest
 
 from tests.conftest import GOLDEN
-from tests.helpers import canon_secret, reference_cases
+from tests.helpers import canon_secret, reference_cases, small_files_batch
 from tools.gen_oracle_fixtures import sample_expect
 from trivy_amd import corpus
 from trivy_amd import secret as S
@@ -65,30 +65,13 @@ def test_corpus_vs_emulation(builtin, chunk):
     assert got == want
 
 
-def _small_files_batch(seed):
-    """Many tiny and empty files (shorter than the K1 warm-up) between normal ones."""
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    big, _ = corpus.make_corpus(1 << 20, seed=seed, plants_per_mib=200)
-    args = []
-    for i in range(big.nfiles):
-        c = bytes(big.data[int(big.offsets[i]):int(big.offsets[i + 1])])
-        args.append(S.ScanArgs(big.path(i), c))
-        if i % 3 == 0:
-            n = int(rng.integers(0, 40))
-            args.append(S.ScanArgs("t/%d.txt" % i, (b"key sk account ghp_ " * 3)[:n]))
-        if i % 7 == 0:
-            args.append(S.ScanArgs("e/%d.txt" % i, b""))
-    return S.Batch.from_args(args)
-
-
 @pytest.mark.parametrize("k1", ["k1f", "automaton"])
 @pytest.mark.parametrize("chunk", [16, 48, 256, 1024])
 def test_k1_matches_reference(builtin, chunk, k1, knob):
     """K1 keyword bits and chunk events are exactly the reference semantics (K1F, the
     default, and the automaton K1 it replaces)."""
     import numpy as np
-    batch = _small_files_batch(chunk)
+    batch = small_files_batch(chunk)
     if k1 == "automaton":
         knob("k1_automaton", 1)
     ctx = S.GpuContext(builtin, 0, chunk_bytes=chunk, adapt_mib=0xFFFFFFFF)
@@ -207,7 +190,7 @@ def test_k1_adaptation_exact(builtin):
 
 
 def test_small_files_vs_cpu_exact(builtin):
-    batch = _small_files_batch(5)
+    batch = small_files_batch(5)
     assert builtin.ScanBatch(batch, device=0) == builtin.ScanBatch(batch, nthreads=16)
 
 

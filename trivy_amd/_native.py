@@ -87,7 +87,8 @@ class Stats(C.Structure):
                 ("event_chunks", C.c_uint32), ("k1_filter", C.c_uint32),
                 ("k1_clock_ms", C.c_double), ("chain_clock_ms", C.c_double), ("post_k1_clock_ms", C.c_double),
                 ("sum_k1_clock_ms", C.c_double), ("sum_chain_clock_ms", C.c_double),
-                ("sum_post_k1_clock_ms", C.c_double)]
+                ("sum_post_k1_clock_ms", C.c_double),
+                ("k2_dense_entries", C.c_uint32), ("k2_rich", C.c_uint32)]
 
 
 # (name, restype, argtypes) -- every symbol include/trivy_secret.h declares
@@ -113,6 +114,9 @@ SIGNATURES = [
     ("tsg_batch_upload", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(C.c_uint32)]),
     ("tsg_batch_kernels", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,
                                     C.POINTER(C.c_uint32), C.c_size_t]),
+    ("tsg_batch_items", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,
+                                  C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32),
+                                  C.c_size_t, _U8P, C.c_size_t, _U64P]),
     ("tsg_batch_collect", C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),
@@ -146,6 +150,10 @@ SIGNATURES = [
                                           C.POINTER(_P)]),
     ("tsg_emulate_candidate_stats", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, _U64P,
                                               _U64P]),
+    ("tsg_emulate_items", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.c_size_t, _U64P, _U64P]),
+    ("tsg_layout_reference", C.c_int, [_U64P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                       _U8P, _U64P]),
     ("tsg_ruleset_rule_plan", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("tsg_emulate_k1", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),

@@ -283,6 +283,51 @@ int tsg_emulate_candidate_stats(const tsg_ruleset* rs, const uint8_t* data,
   }
 }
 
+int tsg_emulate_items(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
+                      uint32_t nfiles, uint32_t chunk, uint32_t max_back, uint32_t* triples,
+                      size_t triples_cap, uint64_t* counts, uint64_t* n_items) {
+  if (!rs || !offsets || chunk == 0) return fail(TSG_ERR_ARG, "bad argument");
+  try {
+    std::vector<uint64_t> poff(nfiles + 1, 0);
+    BatchView b{data, offsets, nfiles, "", poff.data()};
+    std::vector<uint32_t> kw, ev;
+    k1_reference(*rs->plan, b, chunk, &kw, &ev);
+    const size_t G = rs->plan->groups.size();
+    if (counts) std::fill(counts, counts + G, 0);
+    uint64_t n = 0;
+    // (emulate_items visits in (group, file, chunk) order: the triples come out sorted)
+    emulate_items(*rs->plan, b, chunk, kw.data(), ev, max_back, [&](uint32_t g, uint32_t f, uint64_t c) {
+      if (triples && n < triples_cap) {
+        triples[3 * n] = g;
+        triples[3 * n + 1] = f;
+        triples[3 * n + 2] = (uint32_t)c;
+      }
+      if (counts) counts[g]++;
+      n++;
+    });
+    if (n_items) *n_items = n;
+    return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(TSG_ERR_NOMEM, "out of memory");
+  } catch (const std::exception& ex) {
+    return fail(TSG_ERR_INTERNAL, ex.what());
+  }
+}
+
+int tsg_layout_reference(const uint64_t* counts, uint32_t n_groups, uint64_t nchunks, uint64_t items_cap,
+                         uint32_t max_dense, uint8_t* kind, uint64_t* totals) {
+  if ((!counts && n_groups) || !kind) return fail(TSG_ERR_ARG, "bad argument");
+  LayoutTotals t;
+  layout_reference(counts, n_groups, nchunks, items_cap, max_dense, kind, &t);
+  if (totals) {
+    totals[0] = t.extent;
+    totals[1] = t.entries;
+    totals[2] = t.dense_entries;
+    totals[3] = t.skipped;
+  }
+  return TSG_OK;
+}
+
 int tsg_emulate_k1(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
                    uint32_t nfiles, uint32_t chunk, uint32_t* kw, size_t kw_len, uint32_t* ev,
                    size_t ev_len) {

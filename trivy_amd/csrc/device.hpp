@@ -86,12 +86,16 @@ std::shared_ptr<const std::vector<uint8_t>> device_rules_kw_unknown(const Device
 uint32_t device_rules_hot_states(const DeviceRules* d);
 // true: K1 runs as K1F (k1f_kernel, batches under 4 GiB); false: the automaton (k1_kernel)
 bool device_rules_k1_filter(const DeviceRules* d);
+// true: K2's list pass runs k2_kernel_rich (decided by the occupancy API), false: k2_kernel
+bool device_rules_k2_rich(const DeviceRules* d);
 
 int lane_create(DeviceRules* d, LaneState** out);
 void lane_destroy(LaneState* l);
 hipStream_t lane_stream(LaneState* l);
 
-int host_out_alloc(const DeviceRules* d, uint32_t files_cap, HostOut* out);
+// cand_cap: candidate records of one batch (tsg_ctx_options.cand_capacity); K2 drops the
+// records past it and flags their files for whole-file resolution
+int host_out_alloc(const DeviceRules* d, uint32_t files_cap, uint32_t cand_cap, HostOut* out);
 void host_out_free(HostOut* o);
 
 // The device part of one batch on lane `l`, asynchronously; out->ev[kEvDone] completes it.
@@ -102,6 +106,16 @@ int batch_times(const HostOut* out, ScanTimes* t);
 int lane_kw(LaneState* l, uint32_t* kw, size_t n);
 // K1 output of the lane's last batch (test hook): chunk events [nchunks]
 int lane_events(LaneState* l, uint32_t* ev, size_t n);
+// K2's work lists of the lane's last batch as the item passes left them (test hook): list
+// entries {group, first item, n, kind}, dense entries {group, first chunk, n, kind}, the
+// item array (file, chunk) up to the layout's extent (or the array's end: the region of a
+// skipped list group may lie past it), and the skip flags [groups]
+struct LaneItems {
+  std::vector<uint32_t> entries, dentries, items;
+  std::vector<uint8_t> gskip;
+  uint64_t extent = 0;  // the layout's extent (device counter 5)
+};
+int lane_items(LaneState* l, LaneItems* out);
 // K2 per-entry trace of the lane's last batch (TSG_K2_TRACE; empty otherwise): per entry
 // {start, end, group << 32 | items, XCC_ID << 32 | HW_ID}
 int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out);

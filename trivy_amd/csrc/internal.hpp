@@ -1,5 +1,6 @@
 // Shared internals of the C ABI (capi.cpp, gpu.hip).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <memory>
@@ -31,10 +32,23 @@ uint64_t ctx_slot_bytes(const tsg_ctx* c);
 struct Knobs {
   std::atomic<int64_t> tar_range_kib{0}, piece_mib{0}, pike_only{0}, no_k1x{0}, emu_wordrec{0},
       x_step{0}, k1_automaton{0}, group_states{0}, group_table_kib{0}, k1f_grid{0},
-      k1f_list{0};
+      k1f_list{0}, k2_items_cap{0}, k2_max_dense{0}, k2_no_word_recs{0};
   std::mutex m;
   std::string emu_kw_unknown;
 };
 Knobs& knobs();
 std::string knob_kw_unknown();
+
+// K2's item capacity for a batch of nchunks chunks: twice the batch's chunks (the builtin
+// rules list ~11 % of them), at least 64 Ki items; and the number of groups the dense pass
+// takes.  Past either, groups are skipped and resolved on the host.  (Knobs k2_items_cap /
+// k2_max_dense replace them in tests.)
+inline uint64_t k2_items_cap(uint64_t nchunks) {
+  const int64_t k = knobs().k2_items_cap.load();
+  return k > 0 ? (uint64_t)k : std::max<uint64_t>(2 * nchunks, 1u << 16);
+}
+inline uint32_t k2_max_dense() {
+  const int64_t k = knobs().k2_max_dense.load();
+  return k > 0 ? (uint32_t)k : 16u;
+}
 }  // namespace tsg

@@ -39,9 +39,6 @@
 
 namespace tsg {
 
-// how K2 covers a rule group in one batch (layout_kernel)
-enum : uint8_t { kGroupNone = 0, kGroupList = 1, kGroupDense = 2, kGroupSkip = 3 };
-
 #define HIP_TRY(x)                                                                    \
   do {                                                                                \
     hipError_t e_ = (x);                                                              \
@@ -73,7 +70,7 @@ constexpr int kPad = 256;     // zero bytes before and after the batch in HBM (>
 #ifndef ITEMS_BPC
 #define ITEMS_BPC 8  // item passes: blocks per CU
 #endif
-constexpr int kMaxBack = 16;  // event windows up to this many chunks; larger -> whole file
+constexpr int kMaxBack = (int)kMaxBackChunks;  // event windows up to this many chunks; larger -> whole file
 
 // ---------------------------------------------------------------- device tables
 // K2 tables name a state by its row (state * nc): next = tab[row + class] needs no
@@ -1816,6 +1813,7 @@ struct LayoutArgs {
 constexpr int kK2Block = K2_LIST_BLOCK;
 constexpr uint32_t kEntryItems = 2 * kK2Block;  // two chains per lane
 constexpr uint32_t kEntryChunks = kStreams * kBlock;
+static_assert(kEntryItems == kK2EntryItems && kEntryChunks == kK2EntryChunks, "layout_reference restates these");
 
 // exclusive prefix sums of N values at once over the block (one LDS exchange, two barriers
 // for all of them); returns the totals in tot.  s_wave: [N * waves]
@@ -3438,6 +3436,7 @@ void device_rules_destroy(DeviceRules* d) { delete d; }
 std::shared_ptr<const std::vector<uint8_t>> device_rules_kw_unknown(const DeviceRules* d) { return d->kw_unknown; }
 uint32_t device_rules_hot_states(const DeviceRules* d) { return d->hot_states; }
 bool device_rules_k1_filter(const DeviceRules* d) { return d->use_k1f; }
+bool device_rules_k2_rich(const DeviceRules* d) { return d->k2_rich; }
 
 int lane_create(DeviceRules* d, LaneState** out) {
   HIP_TRY(hipSetDevice(d->device));
@@ -3473,11 +3472,11 @@ void host_out_free(HostOut* o) {
   *o = HostOut{};
 }
 
-int host_out_alloc(const DeviceRules* d, uint32_t files_cap, HostOut* o) {
+int host_out_alloc(const DeviceRules* d, uint32_t files_cap, uint32_t cand_cap, HostOut* o) {
   HIP_TRY(hipSetDevice(d->device));
   HostOut h;
   h.files_cap = std::max<uint32_t>(files_cap, 1);
-  h.cand_cap = 1u << 22;
+  h.cand_cap = std::max<uint32_t>(cand_cap, 1);
   h.groups = std::max<uint32_t>(1, (uint32_t)d->groups.size());
   h.kw_words = (uint32_t)d->plan->kw_words;
   // one host-mapped block for the small outputs (each part 256-B aligned): counts | gskip |
@@ -3561,10 +3560,10 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   if ((rc = ensure(&l->ggate, &l->ggate_cap, (size_t)F * r->GW + 1))) return rc;
   if ((rc = ensure(&l->ovf, &l->ovf_cap, (size_t)F + 1))) return rc;
   if ((rc = ensure(&l->hascand, &l->hascand_cap, (size_t)F + 1))) return rc;
-  // item capacity: twice the batch's chunks (the builtin rules list ~11 % of them); over
-  // it, groups are skipped (kGroupSkip) and resolved on the host, never dropped
-  const uint64_t items_cap = std::max<uint64_t>(2 * nchunks, 1u << 16);
-  const uint32_t max_dense = 16;
+  // item capacity and dense budget (internal.hpp): over them, groups are skipped
+  // (kGroupSkip) and resolved on the host, never dropped
+  const uint64_t items_cap = k2_items_cap(nchunks);
+  const uint32_t max_dense = k2_max_dense();
   const uint64_t entries_cap = items_cap / kEntryItems + G + 1;
   const uint64_t dentries_cap = (uint64_t)max_dense * ((nchunks + kEntryChunks - 1) / kEntryChunks + 1);
   if ((rc = ensure(&l->items, &l->items_cap, (size_t)items_cap))) return rc;
@@ -3766,7 +3765,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     static const bool diag = getenv("TSG_K2_DIAG") != nullptr;
     A.diag = diag ? l->counts + 8 : nullptr;
     A.claim = l->counts + 12;
-    A.word_recs = G <= 0x3FFF;
+    A.word_recs = G <= 0x3FFF && !knobs().k2_no_word_recs.load();
     static const bool trace = getenv("TSG_K2_TRACE") != nullptr;
     if (trace && (rc = ensure(&l->etrace, &l->etrace_cap, (size_t)entries_cap * kTraceW))) return rc;
     if (trace) HIP_TRY(hipMemsetAsync(l->etrace, 0, sizeof(unsigned long long) * entries_cap * kTraceW, st));
@@ -3868,6 +3867,26 @@ int lane_kw(LaneState* l, uint32_t* kw, size_t n) {
   HIP_TRY(hipSetDevice(l->d->device));
   HIP_TRY(hipStreamSynchronize(l->st));
   if (n) HIP_TRY(hipMemcpy(kw, l->kw, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  return TSG_OK;
+}
+
+int lane_items(LaneState* l, LaneItems* out) {
+  HIP_TRY(hipSetDevice(l->d->device));
+  HIP_TRY(hipStreamSynchronize(l->st));
+  uint32_t counts[8];
+  HIP_TRY(hipMemcpy(counts, l->counts, sizeof(counts), hipMemcpyDeviceToHost));
+  // (the counters are the layout's; the buffers' own sizes bound every copy)
+  const size_t ne = std::min<size_t>(counts[2], l->entries_cap), nd = std::min<size_t>(counts[3], l->dentries_cap),
+               ni = std::min<size_t>(counts[5], l->items_cap), G = l->d->groups.size();
+  out->entries.assign(4 * ne, 0);
+  out->dentries.assign(4 * nd, 0);
+  out->items.assign(2 * ni, 0);
+  out->gskip.assign(G, 0);
+  out->extent = counts[5];
+  if (ne) HIP_TRY(hipMemcpy(out->entries.data(), l->entries, sizeof(uint4) * ne, hipMemcpyDeviceToHost));
+  if (nd) HIP_TRY(hipMemcpy(out->dentries.data(), l->dentries, sizeof(uint4) * nd, hipMemcpyDeviceToHost));
+  if (ni) HIP_TRY(hipMemcpy(out->items.data(), l->items, sizeof(uint2) * ni, hipMemcpyDeviceToHost));
+  if (G) HIP_TRY(hipMemcpy(out->gskip.data(), l->gskip, G, hipMemcpyDeviceToHost));
   return TSG_OK;
 }
 

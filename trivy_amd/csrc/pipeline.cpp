@@ -94,6 +94,7 @@ struct Batch {
   BatchResult br;
   ScanTimes t;
   uint32_t counts[48] = {};
+  uint32_t cand_cap = 0;  // candidate records the kernels (or their emulation) had room for
   double resolve_ms = 0;
   uint64_t files_found = 0;
 };
@@ -130,6 +131,11 @@ struct tsg_ctx {
   std::vector<std::thread> workers;
   bool stopping = false;
   std::multiset<std::thread::id> slot_waiters;  // threads waiting in slot_take
+  // the last tsg_batch_kernels: its lane, slot and the submission count after it
+  // (tsg_batch_items reads that lane while nothing else was enqueued since)
+  LaneState* kernels_lane = nullptr;
+  uint32_t kernels_slot = 0;
+  uint64_t kernels_seq = 0;
 
   ~tsg_ctx() {
     {
@@ -257,14 +263,14 @@ int out_take(tsg_ctx* c, uint32_t nfiles, int* idx) {
   for (size_t i = 0; i < c->outs.size(); i++)  // grow a free one
     if (!c->out_busy[i]) {
       host_out_free(&c->outs[i]);
-      int rc = host_out_alloc(c->dr, (uint32_t)std::min<uint64_t>(round_up(nfiles, 65536), 0xFFFFFFF0u), &c->outs[i]);
+      int rc = host_out_alloc(c->dr, (uint32_t)std::min<uint64_t>(round_up(nfiles, 65536), 0xFFFFFFF0u), c->opt.cand_capacity, &c->outs[i]);
       if (rc) return rc;
       c->out_busy[i] = 1;
       *idx = (int)i;
       return TSG_OK;
     }
   HostOut h;
-  int rc = host_out_alloc(c->dr, (uint32_t)std::min<uint64_t>(round_up(std::max<uint32_t>(nfiles, 1), 65536), 0xFFFFFFF0u), &h);
+  int rc = host_out_alloc(c->dr, (uint32_t)std::min<uint64_t>(round_up(std::max<uint32_t>(nfiles, 1), 65536), 0xFFFFFFF0u), c->opt.cand_capacity, &h);
   if (rc) return rc;
   c->outs.push_back(h);
   c->out_busy.push_back(1);
@@ -295,7 +301,9 @@ void update_stats(tsg_ctx* c, const Batch& b) {
   s.resolve_ms = b.resolve_ms;
   s.bytes = b.bytes;
   s.candidates = b.counts[0];
-  s.overflow = b.counts[0] > (c->opt.cand_capacity ? c->opt.cand_capacity : (1u << 22)) ? 1 : 0;
+  s.overflow = b.counts[0] > b.cand_cap ? 1 : 0;
+  s.k2_dense_entries = b.counts[3];
+  s.k2_rich = c->dr && device_rules_k2_rich(c->dr) ? 1u : 0u;
   s.k2_items = b.counts[5];
   s.k2_bytes = (uint64_t)b.counts[5] * c->opt.chunk_bytes;
   s.k2_launches = b.counts[6];
@@ -339,9 +347,24 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
     KernelOutput emu;
     KernelOutputView kv;
     if (c->emulate) {
-      emulate_kernels(*rs->plan, view, c->opt.chunk_bytes, c->opt.ext_cap, &emu);
+      // the device's rules on top of the algorithm: its every-chunk groups, its layout (a
+      // skipped group has no candidates and is resolved on the host) and its candidate capacity
+      EmuOptions eo;
+      eo.max_back = kMaxBackChunks;
+      eo.layout = true;
+      eo.items_cap = k2_items_cap((view.offsets[view.nfiles] + c->opt.chunk_bytes - 1) / c->opt.chunk_bytes);
+      eo.max_dense = k2_max_dense();
+      eo.cand_cap = c->opt.cand_capacity;
+      EmuStats es;
+      emulate_kernels(*rs->plan, view, c->opt.chunk_bytes, c->opt.ext_cap, &emu, nullptr, &eo, &es);
       kv = emu.view();
-      b->counts[0] = (uint32_t)std::min<size_t>(emu.cand.size(), 0xFFFFFFFFu);
+      auto u32 = [](uint64_t x) { return (uint32_t)std::min<uint64_t>(x, 0xFFFFFFFFu); };
+      b->counts[0] = u32(es.candidates);
+      b->counts[3] = u32(es.layout.dense_entries);
+      b->counts[5] = u32(es.layout.extent);
+      b->counts[6] = u32(es.layout.entries);
+      b->counts[7] = u32(es.layout.skipped);
+      b->cand_cap = c->opt.cand_capacity;
     } else {
       if (hipEventSynchronize(ho.ev[kEvDone]) != hipSuccess) throw std::runtime_error("device batch failed");
       (void)batch_times(&ho, &b->t);
@@ -355,6 +378,7 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       kv.kw = ho.kw;
       kv.cand = ho.cand;
       kv.ncand = std::min<uint32_t>(ho.counts[0], ho.cand_cap);
+      b->cand_cap = ho.cand_cap;
       kv.overflow = ho.ovf;
       kv.sparse_kw = true;  // outputs_kernel: flags and the keyword rows the host reads
       kv.kw_unknown = kwu ? kwu->data() : nullptr;
@@ -788,7 +812,11 @@ int tsg_batch_kernels(tsg_ctx* c, uint32_t slot_id, uint32_t nfiles, uint32_t* k
       (void)batch_times(&ho, &b.t);
       std::memcpy(b.counts, ho.counts, sizeof(b.counts));
       b.bytes = s.off[nfiles];
+      b.cand_cap = ho.cand_cap;
       update_stats(c, b);
+      c->kernels_lane = l;
+      c->kernels_slot = slot_id;
+      c->kernels_seq = c->seq;
       if (kw) rc = lane_kw(l, kw, std::min(kw_len, W * nfiles));
       if (ev && !rc) rc = lane_events(l, ev, ev_len);
       if (const char* tp = getenv("TSG_K1F_TRACE")) {  // append K1F's per-wave trace (measurements)
@@ -811,6 +839,30 @@ int tsg_batch_kernels(tsg_ctx* c, uint32_t slot_id, uint32_t nfiles, uint32_t* k
     c->out_busy[oi] = 0;
     if (e != hipSuccess) return fail(TSG_ERR_GPU, std::string("tsg_batch_kernels: ") + hipGetErrorString(e));
     return rc;
+  });
+}
+
+int tsg_batch_items(tsg_ctx* c, uint32_t slot_id, uint32_t* entries, size_t entries_cap, uint32_t* dentries,
+                    size_t dentries_cap, uint32_t* items, size_t items_cap, uint8_t* gskip, size_t gskip_len,
+                    uint64_t* n) {
+  if (!c || !n) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    // (the context lock, as tsg_batch_kernels: no batch is enqueued on the lane meanwhile)
+    std::lock_guard<std::mutex> g(c->m);
+    if (c->emulate) return fail(TSG_ERR_ARG, "an emulated context has no device work lists");
+    if (!c->kernels_lane || c->kernels_slot != slot_id || c->kernels_seq != c->seq)
+      return fail(TSG_ERR_ARG, "tsg_batch_items follows tsg_batch_kernels on the same slot");
+    LaneItems li;
+    int rc = lane_items(c->kernels_lane, &li);
+    if (rc) return rc;
+    n[0] = li.entries.size() / 4;
+    n[1] = li.dentries.size() / 4;
+    n[2] = li.extent;
+    if (entries) std::memcpy(entries, li.entries.data(), 16 * std::min<size_t>(entries_cap, n[0]));
+    if (dentries) std::memcpy(dentries, li.dentries.data(), 16 * std::min<size_t>(dentries_cap, n[1]));
+    if (items) std::memcpy(items, li.items.data(), 8 * std::min<size_t>(items_cap, li.items.size() / 2));
+    if (gskip) std::memcpy(gskip, li.gskip.data(), std::min(gskip_len, li.gskip.size()));
+    return TSG_OK;
   });
 }
 

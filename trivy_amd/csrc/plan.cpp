@@ -1537,47 +1537,105 @@ static void emulate_words(const DFA& d, uint32_t gi, const std::vector<uint32_t>
   if (q >= fe && !d.dead[s]) eot(s);
 }
 
-void emulate_kernels(const Plan& plan, const BatchView& bv, uint32_t chunk, uint32_t ext_cap,
-                     KernelOutput* ko, std::vector<uint64_t>* group_item_bytes) {
+void emulate_items(const Plan& plan, const BatchView& bv, uint32_t chunk, const uint32_t* kwbits,
+                   const std::vector<uint32_t>& ev, uint32_t max_back,
+                   const std::function<void(uint32_t g, uint32_t f, uint64_t c)>& visit) {
   const uint32_t F = bv.nfiles;
-  const bool word_recs = knobs().emu_wordrec.load() && plan.groups.size() <= 0x3FFF;
-  std::vector<uint32_t> ev;
-  k1_reference(plan, bv, chunk, &ko->kw, &ev);
-  ko->cand.clear();
-  ko->overflow.assign(F, 0);
-  if (group_item_bytes) group_item_bytes->assign(plan.groups.size(), 0);
   for (size_t gi = 0; gi < plan.groups.size(); gi++) {
     const GroupPlan& g = plan.groups[gi];
     const uint32_t back = group_back(g, chunk);
-    const DFA& d = *g.dfa;
+    const bool every = (g.events & kEvAlways) != 0 || back > max_back;
     for (uint32_t f = 0; f < F; f++) {
       const uint64_t fs = bv.offsets[f], fe = bv.offsets[f + 1];
       if (fe == fs) continue;
-      const uint32_t* kw = ko->kw.data() + (size_t)f * plan.kw_words;
+      const uint32_t* kw = kwbits + (size_t)f * plan.kw_words;
       bool gate = g.always;
       for (int w = 0; w < plan.kw_words && !gate; w++) gate = (kw[w] & g.kwmask[w]) != 0;
       if (!gate) continue;
       const uint64_t c0 = fs / chunk, c1 = (fe - 1) / chunk;
       for (uint64_t c = c0; c <= c1; c++) {
-        bool need = (g.events & kEvAlways) != 0;
+        bool need = every;
         for (uint64_t q = c; q <= std::min<uint64_t>(c + back, c1) && !need; q++) need = (ev[q] & g.events) != 0;
-        if (!need) continue;
-        const uint64_t a = std::max<uint64_t>(fs, c * chunk), b = std::min<uint64_t>(fe, (c + 1) * chunk);
-        if (group_item_bytes) (*group_item_bytes)[gi] += b - a;
-        if (word_recs) {
-          emulate_words(d, (uint32_t)gi, g.rules, bv.data, f, fs, fe, a, b, ext_cap, &ko->cand);
-          continue;
-        }
-        bool o = run_segment(d, bv.data, fs, fe, a, b, ext_cap, [&](uint32_t mi, uint64_t pos) {
-          const auto& m = d.masks[mi];
-          for (size_t k = 0; k < g.rules.size(); k++)
-            if ((m[k / 64] >> (k % 64)) & 1) ko->cand.push_back({f, g.rules[k], (uint32_t)pos});
-        });
-        if (o)  // a tail past ext_cap: the group's rules over the whole file (kCandWhole)
-          for (uint32_t r : g.rules) ko->cand.push_back({f, r, kCandWhole});
+        if (need) visit((uint32_t)gi, f, c);
       }
     }
   }
+}
+
+void layout_reference(const uint64_t* counts, uint32_t ngroups, uint64_t nchunks, uint64_t items_cap,
+                      uint32_t max_dense, uint8_t* kind, LayoutTotals* totals) {
+  LayoutTotals t;
+  const uint64_t dense_all = (nchunks + kK2EntryChunks - 1) / kK2EntryChunks;
+  uint64_t dense_wanted = 0;
+  for (uint32_t g = 0; g < ngroups; g++) {
+    const uint64_t cnt = counts[g];
+    uint8_t k = kGroupNone;
+    if (cnt * 2 > nchunks) {  // dense budget, in group order
+      k = dense_wanted++ < max_dense ? kGroupDense : kGroupSkip;
+      if (k == kGroupDense) t.dense_entries += dense_all;
+    } else if (cnt) {  // then the item capacity; the region is kept either way
+      k = t.extent + cnt <= items_cap ? kGroupList : kGroupSkip;
+      if (k == kGroupList) t.entries += (cnt + kK2EntryItems - 1) / kK2EntryItems;
+      t.extent += cnt;
+    }
+    t.skipped += k == kGroupSkip;
+    if (kind) kind[g] = k;
+  }
+  if (totals) *totals = t;
+}
+
+void emulate_kernels(const Plan& plan, const BatchView& bv, uint32_t chunk, uint32_t ext_cap,
+                     KernelOutput* ko, std::vector<uint64_t>* group_item_bytes, const EmuOptions* opt,
+                     EmuStats* st) {
+  const uint32_t F = bv.nfiles;
+  const size_t G = plan.groups.size();
+  const bool word_recs = knobs().emu_wordrec.load() && !knobs().k2_no_word_recs.load() && G <= 0x3FFF;
+  const uint32_t max_back = opt ? opt->max_back : 0xFFFFFFFFu;
+  std::vector<uint32_t> ev;
+  k1_reference(plan, bv, chunk, &ko->kw, &ev);
+  ko->cand.clear();
+  ko->overflow.assign(F, 0);
+  ko->group_skipped.clear();
+  if (group_item_bytes) group_item_bytes->assign(G, 0);
+  std::vector<uint8_t> kind;
+  EmuStats es;
+  if (opt && opt->layout) {
+    std::vector<uint64_t> counts(G, 0);
+    emulate_items(plan, bv, chunk, ko->kw.data(), ev, max_back, [&](uint32_t g, uint32_t, uint64_t) { counts[g]++; });
+    kind.resize(G);
+    layout_reference(counts.data(), (uint32_t)G, ev.size(), opt->items_cap, opt->max_dense, kind.data(), &es.layout);
+    if (es.layout.skipped) {
+      ko->group_skipped.assign(G, 0);
+      for (size_t g = 0; g < G; g++) ko->group_skipped[g] = kind[g] == kGroupSkip;
+    }
+  }
+  emulate_items(plan, bv, chunk, ko->kw.data(), ev, max_back, [&](uint32_t gi, uint32_t f, uint64_t c) {
+    if (!kind.empty() && kind[gi] == kGroupSkip) return;  // left to the host (group_skipped)
+    const GroupPlan& g = plan.groups[gi];
+    const DFA& d = *g.dfa;
+    const uint64_t fs = bv.offsets[f], fe = bv.offsets[f + 1];
+    const uint64_t a = std::max<uint64_t>(fs, c * chunk), b = std::min<uint64_t>(fe, (c + 1) * chunk);
+    if (group_item_bytes) (*group_item_bytes)[gi] += b - a;
+    if (word_recs) {
+      emulate_words(d, gi, g.rules, bv.data, f, fs, fe, a, b, ext_cap, &ko->cand);
+      return;
+    }
+    bool o = run_segment(d, bv.data, fs, fe, a, b, ext_cap, [&](uint32_t mi, uint64_t pos) {
+      const auto& m = d.masks[mi];
+      for (size_t k = 0; k < g.rules.size(); k++)
+        if ((m[k / 64] >> (k % 64)) & 1) ko->cand.push_back({f, g.rules[k], (uint32_t)pos});
+    });
+    if (o)  // a tail past ext_cap: the group's rules over the whole file (kCandWhole)
+      for (uint32_t r : g.rules) ko->cand.push_back({f, r, kCandWhole});
+  });
+  es.candidates = ko->cand.size();
+  // the candidate buffer's capacity, as emit_cand applies it: a record past it is dropped
+  // and its file resolved whole
+  if (opt && ko->cand.size() > opt->cand_cap) {
+    for (size_t i = (size_t)opt->cand_cap; i < ko->cand.size(); i++) ko->overflow[ko->cand[i].file] = 1;
+    ko->cand.resize((size_t)opt->cand_cap);
+  }
+  if (st) *st = es;
 }
 
 }  // namespace tsg

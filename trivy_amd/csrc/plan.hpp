@@ -11,6 +11,7 @@
 //   resolver (host)        : candidate end offsets -> exact windows -> scan_file.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -149,6 +150,30 @@ struct KernelOutputView {
   const uint8_t* group_skipped = nullptr;
 };
 
+// How K2 covers a rule group in one batch (kernels.hip layout_block, layout_reference).
+enum : uint8_t { kGroupNone = 0, kGroupList = 1, kGroupDense = 2, kGroupSkip = 3 };
+// The device's item rules: a group whose event window is longer than kMaxBackChunks chunks
+// listens to every chunk of its gated files; a list entry holds up to kK2EntryItems items
+// of one group, a dense entry kK2EntryChunks consecutive chunks of the batch.
+constexpr uint32_t kMaxBackChunks = 16;
+constexpr uint32_t kK2EntryItems = 512;
+constexpr uint32_t kK2EntryChunks = 1024;
+
+// layout_block's decision restated on the host, groups in id order: a group whose items
+// cover more than half of the batch's chunks wants the dense pass and gets it while fewer
+// than max_dense groups before it wanted it; every other group with items wants a region of
+// the item array at the sum of the list-wanting counts before it (a skipped group keeps its
+// region) and is listed when that region ends within items_cap.  A group with items that
+// gets neither is skipped.
+struct LayoutTotals {
+  uint64_t extent = 0;         // item array in use: regions of every list-wanting group
+  uint64_t entries = 0;        // list entries
+  uint64_t dense_entries = 0;  // dense entries
+  uint64_t skipped = 0;        // skipped groups
+};
+void layout_reference(const uint64_t* counts, uint32_t ngroups, uint64_t nchunks, uint64_t items_cap,
+                      uint32_t max_dense, uint8_t* kind, LayoutTotals* totals);
+
 // Everything the kernels hand back for one batch.
 struct KernelOutput {
   std::vector<uint32_t> kw;        // [nfiles * kw_words]
@@ -159,6 +184,8 @@ struct KernelOutput {
   // [nfiles] (or empty): Global.AllowPath of each path computed on the device:
   // 0 / 1, or 2 = non-ASCII path, decided on the host
   std::vector<uint8_t> path_ok;
+  // [groups] (or empty): 1 = the layout skipped the group, it has no candidates
+  std::vector<uint8_t> group_skipped;
   KernelOutputView view() const {
     KernelOutputView v;
     v.kw = kw.data();
@@ -167,6 +194,7 @@ struct KernelOutput {
     v.overflow = overflow.empty() ? nullptr : overflow.data();
     v.kw_unknown = kw_unknown.empty() ? nullptr : kw_unknown.data();
     v.path_ok = path_ok.empty() ? nullptr : path_ok.data();
+    v.group_skipped = group_skipped.empty() ? nullptr : group_skipped.data();
     return v;
   }
 };
@@ -193,8 +221,31 @@ void scan_batch_cpu(const Ruleset& rs, const BatchView& b, int nthreads,
 // CPU emulation of the two kernels' algorithm (same chunking, same tables);
 // used by the CPU tests and as the reference for the HIP kernels.
 // group_item_bytes (optional, [groups]): bytes of the K2 items of each group.
+// opt (optional): the device's rules on top of the algorithm, as an emulated context
+// applies them; st (optional): what the device would count.
+struct EmuOptions {
+  uint32_t max_back = 0xFFFFFFFFu;  // emulate_items' max_back (the device: kMaxBackChunks)
+  bool layout = false;              // layout_reference decides: a skipped group has no candidates
+  uint64_t items_cap = 0;
+  uint32_t max_dense = 0;
+  uint64_t cand_cap = ~0ull;  // records past it are dropped and their files flagged (overflow)
+};
+struct EmuStats {
+  uint64_t candidates = 0;  // records produced, dropped ones included
+  LayoutTotals layout;
+};
 void emulate_kernels(const Plan& plan, const BatchView& b, uint32_t chunk, uint32_t ext_cap,
-                     KernelOutput* ko, std::vector<uint64_t>* group_item_bytes = nullptr);
+                     KernelOutput* ko, std::vector<uint64_t>* group_item_bytes = nullptr,
+                     const EmuOptions* opt = nullptr, EmuStats* st = nullptr);
+
+// The item set K2 scans, given K1's output (kw [nfiles * kw_words], ev [chunks]): visit(g, f,
+// c) for every group g, file f and chunk c, in that order, such that g is gated for f
+// (always, or kw & kwmask), c is a chunk of f, and some chunk in [c, min(c + back_g, last
+// chunk of f)] carries one of g's event bits.  Empty files have no items.  A group with
+// back_g > max_back listens to every chunk (the device: kMaxBackChunks; 0xFFFFFFFF: never).
+void emulate_items(const Plan& plan, const BatchView& b, uint32_t chunk, const uint32_t* kw,
+                   const std::vector<uint32_t>& ev, uint32_t max_back,
+                   const std::function<void(uint32_t g, uint32_t f, uint64_t c)>& visit);
 
 // K1 semantics shared by the HIP kernel and the emulation: keyword bits of every file
 // [nfiles * kw_words] and event bits of every chunk c = bytes [c*chunk, (c+1)*chunk).

@@ -295,6 +295,38 @@ class Scanner:
                                        ev.ctypes.data_as(u32p), ev.size))
         return kw.reshape(batch.nfiles, W), ev
 
+    def emulate_items(self, batch, chunk, max_back=16):
+        """The item set K2 scans (tsg_emulate_items): sorted (group, file, chunk) triples
+        [n, 3] and the items per group.  max_back 16 is the device's every-chunk rule,
+        0xFFFFFFFF the emulation's."""
+        G = self.info()["n_groups"]
+        counts = np.zeros(max(G, 1), dtype=np.uint64)
+        n = C.c_uint64()
+        u64p = C.POINTER(C.c_uint64)
+        args = (self.handle, C.c_void_p(batch.data.ctypes.data), batch.offsets.ctypes.data_as(u64p),
+                batch.nfiles, chunk, max_back)
+        N.check(N.lib().tsg_emulate_items(*args, None, 0, counts.ctypes.data_as(u64p), C.byref(n)))
+        tri = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
+        N.check(N.lib().tsg_emulate_items(*args, tri.ctypes.data_as(C.POINTER(C.c_uint32)), n.value,
+                                          None, None))
+        return tri[:n.value], counts[:G]
+
+    def candidate_stats(self, batch, chunk):
+        """tsg_emulate_candidate_stats: (candidate ends per rule, K2 item bytes per group)."""
+        per_rule = np.zeros(max(len(self.Rules), 1), dtype=np.uint64)
+        per_group = np.zeros(max(self.info()["n_groups"], 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        N.check(N.lib().tsg_emulate_candidate_stats(
+            self.handle, C.c_void_p(batch.data.ctypes.data), batch.offsets.ctypes.data_as(u64p),
+            batch.nfiles, chunk, per_rule.ctypes.data_as(u64p), per_group.ctypes.data_as(u64p)))
+        return per_rule[:len(self.Rules)], per_group[:self.info()["n_groups"]]
+
+    def rule_group(self, rule):
+        """Plan introspection: the K2 group of rule index `rule` (-1: host only)."""
+        g, relax, ml = C.c_int32(), C.c_int32(), C.c_int64()
+        N.check(N.lib().tsg_ruleset_rule_plan(self.handle, rule, C.byref(g), C.byref(relax), C.byref(ml)))
+        return g.value
+
     def k1_literals(self):
         """K1's literals as (bytes, event bits); ids below n_keywords are keywords."""
         out = []
@@ -366,6 +398,29 @@ class Scanner:
         buf = C.string_at(ptr, n.value)
         L.tsg_result_free(out)
         return decode_results(buf, paths, self.Rules)
+
+
+GROUP_NONE, GROUP_LIST, GROUP_DENSE, GROUP_SKIP = 0, 1, 2, 3
+ENTRY_ITEMS, ENTRY_CHUNKS = 512, 1024  # a K2 list entry's items, a dense entry's chunks
+
+
+def default_items_cap(nchunks):
+    """K2's item capacity for a batch of nchunks chunks without the k2_items_cap knob."""
+    return max(2 * nchunks, 1 << 16)
+
+
+def layout_reference(counts, nchunks, items_cap, max_dense=16):
+    """tsg_layout_reference: (kind per group, totals) of the device's item layout."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    kind = np.zeros(max(len(counts), 1), dtype=np.uint8)
+    tot = np.zeros(4, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    N.check(N.lib().tsg_layout_reference(counts.ctypes.data_as(u64p), len(counts), int(nchunks),
+                                         int(items_cap), int(max_dense),
+                                         kind.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         tot.ctypes.data_as(u64p)))
+    return kind[:len(counts)], {"items": int(tot[0]), "entries": int(tot[1]),
+                                "dense_entries": int(tot[2]), "skipped": int(tot[3])}
 
 
 def decode_results(buf, paths, rules):
@@ -478,6 +533,26 @@ class GpuContext:
         N.check(N.lib().tsg_batch_kernels(self._h, sid, b.nfiles, kw.ctypes.data_as(u32p), kw.size,
                                           ev.ctypes.data_as(u32p), ev.size))
         self._k1 = (kw.reshape(b.nfiles, W), ev)
+
+    def batch_items(self):
+        """K2's work lists of the last kernels() call (tsg_batch_items): list entries [n, 4]
+        {group, first item, items, kind}, dense entries [n, 4] {group, first chunk, chunks,
+        kind}, the item array [n, 2] (file, chunk) and the skip flag of every group."""
+        sid, _ = self._upload
+        G = self.scanner.info()["n_groups"]
+        n = (C.c_uint64 * 3)()
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        N.check(N.lib().tsg_batch_items(self._h, sid, None, 0, None, 0, None, 0, None, 0, n))
+        ent = np.zeros((max(n[0], 1), 4), dtype=np.uint32)
+        dent = np.zeros((max(n[1], 1), 4), dtype=np.uint32)
+        items = np.zeros((max(n[2], 1), 2), dtype=np.uint32)
+        gskip = np.zeros(max(G, 1), dtype=np.uint8)
+        m = (C.c_uint64 * 3)()
+        N.check(N.lib().tsg_batch_items(self._h, sid, ent.ctypes.data_as(u32p), n[0],
+                                        dent.ctypes.data_as(u32p), n[1], items.ctypes.data_as(u32p), n[2],
+                                        gskip.ctypes.data_as(u8p), G, m))
+        assert list(m) == list(n)
+        return ent[:n[0]], dent[:n[1]], items[:n[2]], gskip[:G]
 
     def k1_output(self, chunk):
         """(keyword bits [nfiles, kw_words], chunk event bits) of the last kernels() call."""
