@@ -35,10 +35,7 @@ struct HostOut {
   uint8_t* gskip = nullptr;     // [groups] 1 = K2 skipped the group (item capacity)
   Candidate* cand = nullptr;    // [cand_cap] host-mapped: K2 candidates copied out
   Candidate* cand_dev = nullptr;  // device address of `cand`
-  uint32_t* counts = nullptr;   // [48] 0 candidates, 1 event chunks, 2 K2 list entries,
-                                // 3 dense entries, 5 items, 6 entries, 7 skipped groups,
-                                // 8-11 K2 diagnostics (TSG_K2_DIAG), 14-15 K1X, 16-17 K1F,
-                                // 32-39 kernel clock stamps (u64)
+  uint32_t* counts = nullptr;   // [kCounts] the batch's counter block (CountSlot)
   uint32_t files_cap = 0, cand_cap = 0, groups = 0, kw_words = 0;
   uint32_t wall_khz = 0;        // the device wall clock's rate (hipDeviceAttributeWallClockRate)
   // stage boundaries of the batch on its lane's stream: data H2D | offsets H2D | prep |
@@ -48,6 +45,41 @@ struct HostOut {
 };
 
 constexpr int kEvDone = 8;
+
+// The per-batch counter block: u32 slots in HBM (LaneState::counts; prep zeroes them, the
+// kernels count into them) which the outputs kernel copies whole to HostOut::counts.  This
+// enumeration is the only place the layout is written: the kernels get pointers to their
+// slots, the host names every slot it reads.
+enum CountSlot : uint32_t {
+  kCntCand = 0,          // candidate records K2 reserved (past cand_cap: dropped, file flagged)
+  kCntEvChunks = 1,      // event chunks listed (the length of the event list)
+  kCntListEntries = 2,   // K2 list entries of the work list (K2Args::nentries)
+  kCntDenseEntries = 3,  // K2 dense entries (K2Args::ndentries)
+  kCntLayout = 4,        // base of LayoutArgs::stats; its slots are kCntLayout + LayoutStat
+  kCntItems = 5,         // items the layout placed (tsg_stats k2_items)
+  kCntEntries = 6,       // list entries the layout wrote (k2_launches)
+  kCntSkipped = 7,       // groups K2 skipped (groups_skipped)
+  kCntK2Diag = 8,        // [4] K2Args::diag (TSG_K2_DIAG): tail bytes, longest tail, tails
+                         // over 4 KiB, word replays
+  kCntK2Claim = 12,      // [2] K2Args::claim: next list entry, next dense entry
+  kCntK1X = 14,          // [2] K1XArgs::stats: records listed, words verified inline
+  kCntK1F = 16,          // [2] K1FArgs::stats: words listed, verified arrivals
+  kCntK1FSample = 24,    // [2] the same pair of the K1F adaptation's sampling launch
+  kCntClk = 32,          // [kClkStamps] u64 device wall-clock stamps (ClkStamp)
+  kCounts = 48,
+};
+enum LayoutStat : uint32_t { kLayItems = 1, kLayEntries = 2, kLaySkipped = 3 };  // LayoutArgs::stats[...]
+// The kernels' own spans beside the HIP events around their launches (batch_times).  A
+// start is the atomicMax of the clock's complement (= the minimum) over the first blocks.
+enum ClkStamp : uint32_t { kClkK1FStart = 0, kClkK1FEnd = 1, kClkGatesStart = 2, kClkK2End = 3, kClkStamps = 4 };
+static_assert(kCntDenseEntries < kCntLayout && kCntLayout + kLayItems == kCntItems &&
+                  kCntLayout + kLayEntries == kCntEntries && kCntLayout + kLaySkipped == kCntSkipped,
+              "the layout's stats are slots 5..7");
+static_assert(kCntSkipped < kCntK2Diag && kCntK2Diag + 4 <= kCntK2Claim && kCntK2Claim + 2 <= kCntK1X &&
+                  kCntK1X + 2 <= kCntK1F && kCntK1F + 2 <= kCntK1FSample && kCntK1FSample + 2 <= kCntClk,
+              "counter ranges overlap");
+static_assert(kCntClk % 2 == 0 && kCntClk + 2 * kClkStamps <= kCounts, "clock stamps: 8-byte aligned, inside the block");
+
 // per-batch K2 diagnostics (K2 work that is not the chunks themselves)
 struct K2Diag {
   unsigned long long tail_bytes, tail_max, long_tails, replays;
@@ -113,7 +145,7 @@ int lane_events(LaneState* l, uint32_t* ev, size_t n);
 struct LaneItems {
   std::vector<uint32_t> entries, dentries, items;
   std::vector<uint8_t> gskip;
-  uint64_t extent = 0;  // the layout's extent (device counter 5)
+  uint64_t extent = 0;  // the layout's extent (counter kCntItems)
 };
 int lane_items(LaneState* l, LaneItems* out);
 // K2 per-entry trace of the lane's last batch (TSG_K2_TRACE; empty otherwise): per entry

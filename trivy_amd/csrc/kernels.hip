@@ -13,8 +13,9 @@
 //        verification of the hit positions; ORs keyword and event bits into K1's output.
 //   gates per file: which K2 groups the keyword bits switch on; per chunk: which of those
 //        groups have an event within `back` chunks after it -> (file, chunk) items,
-//        counted; a one-block layout kernel turns the counts into item regions and K2's
-//        work list on the device (no host round trip); the items are then written.
+//        counted; every block of the emit pass then turns the counts into item regions and
+//        K2's work list (layout_block: no host round trip, no launch in between) and writes
+//        its items.
 //   K2   a persistent grid over the work list: each entry is up to 512 items of one rule
 //        group (two DFA chains per lane, quad-transposed loads) or a dense range of the
 //        batch; the group's DFA stays staged in LDS across consecutive entries.  A lane
@@ -47,13 +48,8 @@ namespace tsg {
   } while (0)
 
 constexpr int kStreams = 4;  // K2 dense: chunks per lane
-#ifndef K1_CHAINS
-#define K1_CHAINS 2
-#endif
-#ifndef K1_UNROLL
-#define K1_UNROLL 8  // K1: bytes of a word unrolled (8 of 16: profiles/r04/k1g, 0.394 ms against 0.420 for 16)
-#endif
-constexpr int kK1Chains = K1_CHAINS;  // K1: chains per lane (independent dependent-LDS chains)
+constexpr int kK1Chains = 2;  // K1: chains per lane (independent dependent-LDS chains)
+constexpr int kK1Unroll = 8;  // K1: bytes of a word unrolled (8 of 16: profiles/r04/k1g, 0.394 ms against 0.420 for 16)
 constexpr int kK1Seg = 8;     // K1: consecutive chunks per chain
 // legacy K1 layout: static LDS size classes (KiB): 3, 2 or 1 blocks per CU, of 512, 512
 // and 1024 threads (16 waves per CU at 4 per SIMD, whose registers bound a lane)
@@ -64,12 +60,12 @@ constexpr __host__ __device__ int k1_threads(int ldsk) { return ldsk == 156 ? 10
 // lane reads its own bank) when the automaton leaves room for it; else 256 words
 constexpr uint32_t kK1RepBytes = 256 * 32 * 4;
 constexpr int kBlock = 256;
-constexpr int kCounts = 48;  // per-batch device counters (lane_create); 32..39: kernel clocks
-constexpr int kClk = 32;     // u64 clock stamps at counts + kClk (device wall clock, see K1FArgs::clk)
 constexpr int kPad = 256;     // zero bytes before and after the batch in HBM (>= K1 warm-up)
-#ifndef ITEMS_BPC
-#define ITEMS_BPC 8  // item passes: blocks per CU
-#endif
+constexpr int kItemsBpc = 8;  // item passes: blocks per CU
+// blocks of a launch that stamp its start (ClkStamp): the first ones only -- blocks are
+// dispatched in order, and a same-address atomic at the start of every block of a launch
+// (~850 in the gates pass) queues on one line
+constexpr uint32_t kStampBlocks = 8;
 constexpr int kMaxBack = (int)kMaxBackChunks;  // event windows up to this many chunks; larger -> whole file
 
 // ---------------------------------------------------------------- device tables
@@ -221,7 +217,7 @@ __global__ void __launch_bounds__(256) prep_kernel(PrepArgs A) {
 // aligned on both sides (host_out_alloc, hipMalloc).
 constexpr int kOutCopies = 4;
 struct OutArgs {
-  const uint32_t* count;  // device counters (0 candidates, 7 groups skipped)
+  const uint32_t* count;  // the batch's counter block (kCntCand, kCntSkipped)
   uint32_t cand_cap;
   const uint8_t* cand;  // DevCand records
   uint8_t* cand_host;
@@ -247,10 +243,10 @@ __device__ __forceinline__ void copy_range(uint8_t* __restrict__ d, const uint8_
 
 __global__ void __launch_bounds__(256) outputs_kernel(OutArgs A) {
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  const uint32_t ncand = min(A.count[0], A.cand_cap);
+  const uint32_t ncand = min(A.count[kCntCand], A.cand_cap);
   copy_range(A.cand_host, A.cand, (uint64_t)ncand * 12u, tid, nth);
   for (uint32_t c = 0; c < A.nc; c++) copy_range(A.dst[c], A.src[c], A.n[c], tid, nth);
-  const bool all = A.all_rows || A.count[7] != 0;
+  const bool all = A.all_rows || A.count[kCntSkipped] != 0;
   if (all) copy_range((uint8_t*)A.kw_host, (const uint8_t*)A.kw, (uint64_t)A.F * A.W * 4u, tid, nth);
   for (uint64_t f = tid; f < A.F; f += nth) {
     const uint32_t* row = A.kw + f * A.W;
@@ -435,7 +431,7 @@ struct K1Lane {
       s0[i] = c[i].s;
       top[i] = 0;
     }
-#pragma unroll K1_UNROLL
+#pragma unroll kK1Unroll
     for (int k = 0; k < 16; k++)
 #pragma unroll
       for (int i = 0; i < NS; i++) {
@@ -608,47 +604,30 @@ __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 8))
 // starts sets its bit without a global load, and a literal inside the captured bytes is
 // compared without one: the verification of the last words of the range (which nothing
 // overlaps) costs LDS latency, not HBM round trips under full streaming load.
-#ifndef K1F_QUEUE
-#define K1F_QUEUE 128
-#endif
 #ifndef K1F_SHARES
-#define K1F_SHARES 1  // tile ranges by the waves' SIMD slots (0: equal; measurement builds)
-#endif
-#ifndef K1F_STEAL
-#define K1F_STEAL 0  // 1/K1F_STEAL of a block's tiles claimed in chunks by the first waves done
-#endif               // (0: none; measured without gain, profiles/r06/o: variants fs*, fc*)
-#ifndef K1F_STEAL_CHUNK
-#define K1F_STEAL_CHUNK 8  // tiles per claim
-#endif
-#ifndef K1F_NO_END_ATOMICS
-#define K1F_NO_END_ATOMICS 0  // (1: no block-end counters or stamp; a timing probe only)
+#define K1F_SHARES 1  // tile ranges by the waves' SIMD slots (0: equal; measurement builds, variant "fe")
 #endif
 #ifndef K1F_WTRACE
 #define K1F_WTRACE 0  // per-wave trace (TSG_K1F_TRACE; measurement builds, variant "ftr")
 #endif
-constexpr uint32_t kFQueue = K1F_QUEUE;                    // ring entries (32 B) per wave
-static_assert(kFQueue >= 64 && (kFQueue & (kFQueue - 1)) == 0, "a tile lists up to 64 words");
+// ring entries (32 B) per wave: a tile lists up to 64 words and 64 are verified together, so
+// 128 entries always have room for a tile's words
+constexpr uint32_t kFQueue = 128;
+static_assert(kFQueue >= 128 && (kFQueue & (kFQueue - 1)) == 0, "under 64 listed words before a tile, up to 64 more in it");
 constexpr uint32_t kFEntBytes = 256 * 256;                 // 256 entries x 16 replicas x 16 B
 constexpr uint32_t kFQueueOff = kFEntBytes;
-#ifndef K1F_THREADS
-#define K1F_THREADS 1024
-#endif
-constexpr int kFThreads = K1F_THREADS;                     // one block per CU
+constexpr int kFThreads = 1024;                            // one block per CU
 constexpr uint32_t kFImgOff = kFQueueOff + (kFThreads / 64) * kFQueue * 32;
 constexpr uint32_t kFCfOff = kFImgOff + kFImgMax;
 constexpr uint32_t kFCfMax = 512;                          // coarse file map entries in LDS
-constexpr uint32_t kFStOff = kFCfOff + 4 * kFCfMax;        // block counters (listed, arrivals, reserve claims)
+constexpr uint32_t kFStOff = kFCfOff + 4 * kFCfMax;        // block counters (listed, arrivals, one spare word)
 constexpr uint32_t kFBitsOff = kFStOff + 16;               // the block's event-chunk bitmap (event list)
 constexpr uint32_t kFBitsWords = 3 * kFThreads;             // 12 KiB: 98,304 chunks of the block's range
 constexpr uint32_t kFZoneOff = kFBitsOff + 4 * kFBitsWords;  // zone chunks marked: own [0, 32), next [32, 64) words
 constexpr uint32_t kFZoneChunks = 1024;                     // zone chunks per side (launch_k1f checks)
 constexpr uint32_t kFLds = kFZoneOff + 2 * kFZoneChunks / 8;  // 158 KiB at 1024 threads
 static_assert(kFLds <= 160 * 1024, "K1F's LDS");
-#ifndef K1F_DEPTH
-#define K1F_DEPTH 4
-#endif
-
-constexpr uint32_t kFDepth = K1F_DEPTH;                    // tiles in flight per wave
+constexpr uint32_t kFDepth = 4;                            // tiles in flight per wave (profiles/r05/kv2)
 
 struct DevK1F {
   const uint4* ent;    // [256] entries d_0..d_3
@@ -665,10 +644,11 @@ struct K1FArgs {
   uint32_t* ev;     // zeroed by prep; ORed into
   uint32_t* hits;   // [nlit] verified arrivals per record (sampling pass) or null
   uint32_t* stats;  // [2] listed words, verified arrivals (zeroed by prep)
-  // null, or the batch's clock stamps (u64, zeroed by prep; device wall clock): [0] ~first
-  // block start (atomicMax of the complement = min), [1] last block end; the gates pass
-  // writes [2] ~its first block start, K2 [3] its last block end.  The kernels' own
-  // durations, beside the HIP events around their launches (bench.py reports both).
+  // null, or the batch's clock stamps (ClkStamp; u64, zeroed by prep; device wall clock):
+  // kClkK1FStart ~first block start (atomicMax of the complement = min), kClkK1FEnd last
+  // block end; the gates pass writes kClkGatesStart ~its first block start, K2 kClkK2End its
+  // last block end.  The kernels' own durations, beside the HIP events around their launches
+  // (bench.py reports both).
   unsigned long long* clk;
   // the event list (null: none; the gates pass compacts the events instead): every chunk
   // whose event word K1F makes non-zero, once, in no particular order (ItemArgs::evlist).
@@ -708,19 +688,11 @@ __device__ __forceinline__ uint32_t f_load4u(const uint8_t* data, uint32_t a) { 
 }
 
 // a lane's 16 bytes of a tile, non-temporal (the batch streams through once): K1F 0.255 ->
-// 0.251 ms and K2 0.129 -> 0.122 ms per GiB against default-policy loads (profiles/r05/c3;
-// K1F_NT=0 builds the default policy for measurement)
-#ifndef K1F_NT
-#define K1F_NT 1
-#endif
+// 0.251 ms and K2 0.129 -> 0.122 ms per GiB against default-policy loads (profiles/r05/c3)
 typedef uint32_t f_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 f_tile_load(const uint8_t* p) {
-#if K1F_NT
   const f_u32x4 v = __builtin_nontemporal_load((const f_u32x4*)p);
   return make_uint4(v.x, v.y, v.z, v.w);
-#else
-  return *(const uint4*)p;
-#endif
 }
 
 struct FCarry {  // the previous tile's per-lane window partials and run flags (f_prev)
@@ -733,9 +705,8 @@ struct K1FLane {
   const uint8_t* smem;
   uint32_t lane, lane16;
 
-  // One tile: the lane's 16 bytes v at batch byte pos.  Returns the run events of the word
-  // (kEvRunU / kEvRunD) and the OR of its windows by groups of four (g[i]: ends 4i..4i+3).
-  __device__ __forceinline__ uint4 entry(uint32_t w, int k) const {  // byte k (0..3) of dword w
+  // the entry of byte k (0..3) of dword w, from this lane's replica
+  __device__ __forceinline__ uint4 entry(uint32_t w, int k) const {
     return *(const uint4*)(smem + __builtin_amdgcn_perm(w, lane16, 0x0C0C0000u | ((4u + (uint32_t)k) << 8)));
   }
   // One tile: the lane's 16 bytes v.  Returns the run events of the word (kEvRunU /
@@ -780,31 +751,6 @@ struct K1FLane {
 #pragma unroll
       for (int k = 3; k < 8; k++) r[8 + k] = k1f_and3(e[k - 3].x, e[k - 2].y, e[k - 1].z) & e[k].w;
     }
-#pragma unroll
-    for (int i = 0; i < 4; i++) g[i] = k1f_or3(r[4 * i], r[4 * i + 1], r[4 * i + 2]) | r[4 * i + 3];
-    const uint32_t m = k1f_flags(r[3], r[7], r[11], r[15]);
-    const uint32_t m1 = f_prev(m, cy.m), m2 = f_prev(m1, cy.m1);
-    cy.m = m;
-    cy.m1 = m1;
-    return k1f_runs(m, m1, m2);
-  }
-  // the same with all 16 entries read at once (one LDS round trip per tile, 64 VGPRs of
-  // entries; measurement build K1F_ALL16)
-  __device__ __forceinline__ uint32_t tile16(uint4 v, FCarry& cy, uint32_t (&g)[4]) const {
-    uint4 e[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) e[k] = entry(k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w, k & 3);
-    const uint32_t ao = k1f_and3(e[13].x, e[14].y, e[15].z), bo = e[14].x & e[15].y, co = e[15].x;
-    const uint32_t ai = f_prev(ao, cy.a), bi = f_prev(bo, cy.b), ci = f_prev(co, cy.c);
-    cy.a = ao;
-    cy.b = bo;
-    cy.c = co;
-    uint32_t r[16];
-    r[0] = ai & e[0].w;
-    r[1] = k1f_and3(bi, e[0].z, e[1].w);
-    r[2] = k1f_and3(ci, e[0].y, e[1].z) & e[2].w;
-#pragma unroll
-    for (int k = 3; k < 16; k++) r[k] = k1f_and3(e[k - 3].x, e[k - 2].y, e[k - 1].z) & e[k].w;
 #pragma unroll
     for (int i = 0; i < 4; i++) g[i] = k1f_or3(r[4 * i], r[4 * i + 1], r[4 * i + 2]) | r[4 * i + 3];
     const uint32_t m = k1f_flags(r[3], r[7], r[11], r[15]);
@@ -944,8 +890,8 @@ struct K1FVerify {
 
 __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[kFLds];
-  if (A.clk && threadIdx.x == 0 && blockIdx.x < 8)  // (the first blocks dispatched: GATES_STAMPS)
-    atomicMax(&A.clk[0], ~(unsigned long long)wall_clock64());
+  if (A.clk && threadIdx.x == 0 && blockIdx.x < kStampBlocks)  // (the first blocks dispatched)
+    atomicMax(&A.clk[kClkK1FStart], ~(unsigned long long)wall_clock64());
   {  // the entries (replicated) and the image, every load issued before the stores
     constexpr uint32_t kRep = 256u * 16u / kFThreads, kImg = kFImgMax / 16 / kFThreads;
     uint4 e[kRep], m[kImg];
@@ -975,7 +921,7 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   uint32_t* lcf = (uint32_t*)(smem + kFCfOff);
   for (uint32_t i = threadIdx.x; i < ncl; i += blockDim.x) lcf[i] = A.cf[kc0 + i];
   uint32_t* bst = (uint32_t*)(smem + kFStOff);  // listed words, arrivals
-  if (threadIdx.x < 3) bst[threadIdx.x] = 0;
+  if (threadIdx.x < 3) bst[threadIdx.x] = 0;  // (and the spare word: the measured machine code)
   // the event list: the block's non-zone chunks [c_lo, c_hi) in the LDS bitmap, the zone
   // chunks in the zone bitmaps
   uint32_t* lbm = (uint32_t*)(smem + kFBitsOff);
@@ -999,29 +945,25 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   // measured with the previous shares, three rounds from equal ranges (k1ftrace.py
   // "shares_next"; 0.248 -> 0.2298 -> 0.2227 -> 0.2196 ms per GiB, profiles/r06/l, m, o).
   // (Any split is correct: each wave scans its own contiguous range after the tile before.)
-  // With K1F_STEAL the last 1/K1F_STEAL of the block's tiles is a reserve [bs, bt1) the
-  // waves claim in chunks of K1F_STEAL_CHUNK tiles (an LDS counter) once their own range is
-  // done.  The shares leave a block's waves 16-32 us apart at the end; the reserve evens
-  // them out (every slot's waves 201-203 us) but the launch is no shorter: the blocks' own
-  // means differ by as much (189-200 us), and every chunk restarts the load queue
-  // (profiles/r06/o: 0.2191-0.2205 ms per GiB for 1/8 and 1/16, 0.227 for 1/4, shares
-  // alone 0.2193-0.2199).
-  uint32_t t0, t1, bs, bt1;
+  // The shares leave a block's waves 16-32 us apart at the end.  (A reserve of the block's
+  // last tiles, claimed in chunks by the waves done first, evened them out but the launch
+  // was no shorter -- the blocks' own means differ by as much, and every chunk restarted the
+  // load queue: profiles/r06/o.  It is no longer in the source: a wave scans one range.)
+  uint32_t t0, t1;
   {
     const uint64_t bt0 = (uint64_t)blockIdx.x * wpb * A.ntiles / nw;
-    bt1 = (uint32_t)((uint64_t)(blockIdx.x + 1) * wpb * A.ntiles / nw);
-    bs = K1F_STEAL ? bt1 - (uint32_t)((bt1 - bt0) / K1F_STEAL) : bt1;
+    const uint32_t bt1 = (uint32_t)((uint64_t)(blockIdx.x + 1) * wpb * A.ntiles / nw);
 #if K1F_SHARES
     constexpr uint32_t kShare[4] = {361, 282, 207, 150};  // per slot: its speed, all four slots busy
     const uint32_t tot = (wpb / 4) * (kShare[0] + kShare[1] + kShare[2] + kShare[3]);
     uint32_t before = 0;
     for (uint32_t w = 0; w < wave; w++) before += kShare[(w * 4 / wpb) & 3];
     const uint32_t mine = kShare[(wave * 4 / wpb) & 3];
-    t0 = (uint32_t)(bt0 + (bs - bt0) * before / tot);
-    t1 = (uint32_t)(bt0 + (bs - bt0) * (before + mine) / tot);
+    t0 = (uint32_t)(bt0 + (bt1 - bt0) * before / tot);
+    t1 = (uint32_t)(bt0 + (bt1 - bt0) * (before + mine) / tot);
 #else
-    t0 = (uint32_t)(bt0 + (bs - bt0) * wave / wpb);
-    t1 = (uint32_t)(bt0 + (bs - bt0) * (wave + 1) / wpb);
+    t0 = (uint32_t)(bt0 + (bt1 - bt0) * wave / wpb);
+    t1 = (uint32_t)(bt0 + (bt1 - bt0) * (wave + 1) / wpb);
 #endif
   }
 #if K1F_WTRACE
@@ -1032,7 +974,7 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   }
 #endif
   uint32_t ntile = 0;  // (trace: tiles this wave scanned)
-  if (t0 < t1 || bs < bt1) {  // (waves without tiles wait at the block barrier below)
+  if (t0 < t1) {  // (waves without tiles wait at the block barrier below)
   const K1FLane L{d, A, smem, lane, (lane & 15u) << 4};
   uint4* ring = (uint4*)(smem + kFQueueOff) + 2 * wave * kFQueue;  // 2 x uint4 per entry
   uint32_t qh = 0, qn = 0, nlisted = 0, narr = 0;
@@ -1059,14 +1001,12 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   // lane), so its verification reads LDS, not the batch; 64 listed words are verified
   // together.  The batch has a zero tail of 8 KiB: no load leaves the batch and its tail.
   const uint8_t* base = A.data + 16u * lane;
-  auto body = [&](uint4 v, uint32_t t) __attribute__((always_inline)) {
+  // (captures in the order the measured builds had them: it lays out the closure)
+  auto body = [&lane, &L, &cy, &g, &A, &mark, &qn, &drain, &vw, &qh, &ring, &nlisted](uint4 v, uint32_t t)
+      __attribute__((always_inline)) {
     const uint32_t pos = t * kFTile + 16u * lane;
-#if K1F_ALL16
-    const uint32_t rb = L.tile16(v, cy, g);
-#else
     const uint32_t rb = L.tile(v, cy, g);
-#endif
-      // run events: one atomic per chunk (the leader lane of each chunk in the tile)
+    // run events: one atomic per chunk (the leader lane of each chunk in the tile)
     const uint64_t bu = __ballot(rb & 1u), bd = __ballot(rb & 2u);
     if (__builtin_expect(bu | bd, 0)) {
       const uint32_t c = pos / A.chunk;
@@ -1085,7 +1025,6 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
     const uint64_t hb = __ballot(bun != 0);
     if (__builtin_expect(hb != 0, 0)) {
       const uint32_t n = (uint32_t)__popcll(hb);
-      if (kFQueue < 128 && qn + n > kFQueue) drain(qn);  // (a small ring: room for the tile's words)
       const uint32_t wprev = f_shr1(v.w, vw);  // bytes pos-4 .. pos-1 (all lanes: DPP)
       if (bun) {
         const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(hb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hb, 0u));
@@ -1101,8 +1040,6 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
     }
     vw = __builtin_amdgcn_readlane(v.w, 63);
   };
-  for (;;) {  // the wave's own range, then reserve chunks
-  if (t0 < t1) {
   // the range's loads: the tile before t0 (its carries; zero bytes before the batch) first,
   // then the first kFDepth tiles, so the warm-up waits only for its own load.  The batch has
   // a zero tail of 8 KiB: loads past the last tile stay inside it.
@@ -1136,15 +1073,6 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
   for (uint32_t k = 0; k < kFDepth - 1; k++)
     if (t + k < t1) body(p[k], t + k);
   ntile += t1 - t0;
-  }
-  if (bs >= bt1) break;
-  uint32_t c = 0;
-  if (lane == 0) c = atomicAdd(&bst[2], (uint32_t)K1F_STEAL_CHUNK);
-  c = __builtin_amdgcn_readfirstlane(c);
-  if (c >= bt1 - bs) break;
-  t0 = bs + c;
-  t1 = min(t0 + (uint32_t)K1F_STEAL_CHUNK, bt1);
-  }
   if (qn) drain(qn);
   // the counters: per wave, per block in LDS, one global atomic per block (a same-address
   // atomic from every lane or wave at the end of the kernel serialised into its tail:
@@ -1204,10 +1132,10 @@ __global__ void __launch_bounds__(kFThreads) k1f_kernel(DevK1F d, K1FArgs A) {
       for (uint32_t b = wv[k]; b; b &= b - 1, at++)
         if (at < A.evcap) A.evlist[at] = c_lo + 32 * (threadIdx.x + k * kFThreads) + __builtin_ctz(b);
   }
-  if (threadIdx.x == 0 && !K1F_NO_END_ATOMICS) {
+  if (threadIdx.x == 0) {
     if (bst[0]) atomicAdd(&A.stats[0], bst[0]);
     if (bst[1]) atomicAdd(&A.stats[1], bst[1]);
-    if (A.clk) atomicMax(&A.clk[1], (unsigned long long)wall_clock64());
+    if (A.clk) atomicMax(&A.clk[kClkK1FEnd], (unsigned long long)wall_clock64());
   }
 }
 
@@ -1255,7 +1183,7 @@ struct K1XArgs {
   uint2* list;      // {word index, hit mask}, one slice per k1x_kernel block
   uint32_t* count;  // [blocks] records in each slice
   uint32_t cap;     // records in all slices
-  uint32_t* stats;  // {records listed, words verified inline} (batch counts 14, 15)
+  uint32_t* stats;  // {records listed, words verified inline} (the batch's kCntK1X pair)
 };
 
 __device__ __forceinline__ uint32_t x_lower4(uint32_t x) {
@@ -1276,8 +1204,9 @@ __device__ __forceinline__ uint32_t x_low_byte(uint8_t c) { return (c >= 'A' && 
 
 // exact check of the literals whose 4-gram at some offset j starts at batch byte p (window
 // w = its 4 lowercased bytes): each candidate literal starts at p - j
-#ifdef K1X_DIAG  // measurement builds: slot probes, entries examined, literal matches
-#define K1X_DIAG_ADD(i, v) atomicAdd(&A.stats[(i)], (v))
+#ifdef K1X_DIAG  // measurement builds: slot probes, entries examined, literal matches, counted
+// into the K2 diagnostics' slots i of the counter block (A.stats points at kCntK1X)
+#define K1X_DIAG_ADD(i, v) atomicAdd(&A.stats[(int)kCntK2Diag + (i) - (int)kCntK1X], (v))
 #else
 #define K1X_DIAG_ADD(i, v) ((void)0)
 #endif
@@ -1286,10 +1215,10 @@ __device__ void k1x_verify_at(const DevK1X& x, const K1XArgs& A, uint64_t p, uin
   uint32_t h = (w * 0x85EBCA6Bu) >> x.shift;
   for (;;) {
     const uint4 sl = x.slots[h];
-    K1X_DIAG_ADD(-4, 1u);
+    K1X_DIAG_ADD(2, 1u);
     if (sl.z == 0) return;  // no literal with this 4-gram
     if (sl.x == w) {
-      K1X_DIAG_ADD(-6, sl.z);
+      K1X_DIAG_ADD(0, sl.z);
       for (uint32_t e = 0; e < sl.z; e++) {
         const uint32_t ent = x.lits[sl.y + e];
         const uint32_t i = ent & 0xFFFFFFu, j = ent >> 24;
@@ -1318,7 +1247,7 @@ __device__ void k1x_verify_at(const DevK1X& x, const K1XArgs& A, uint64_t p, uin
           }
         }
         if (!eq) continue;
-        K1X_DIAG_ADD(-5, 1u);
+        K1X_DIAG_ADD(1, 1u);
         const uint64_t q = s + len - 1;
         if (x.ev[i]) atomicOr(&A.ev[q / A.chunk], x.ev[i]);
         const int32_t k = x.kwid[i];
@@ -1334,10 +1263,7 @@ __device__ void k1x_verify_at(const DevK1X& x, const K1XArgs& A, uint64_t p, uin
 }
 
 constexpr int kK1XBlock = 1024;
-#ifndef K1X_WORDS
-#define K1X_WORDS 4
-#endif
-constexpr int kXWords = K1X_WORDS;  // words per lane per round (k1x_kernel)
+constexpr int kXWords = 4;  // words per lane per round (k1x_kernel)
 
 // the window at byte k of a word (d: its dwords and the next word's first)
 __device__ __forceinline__ uint32_t k1x_window(const uint32_t (&d)[5], int k) {
@@ -1526,7 +1452,7 @@ struct ItemArgs {
   uint32_t F, G, GW, chunk, maxback;
   uint32_t* count;            // [G]
   uint32_t* bcount;           // [gridDim.x * G] each count block's place in each group's items
-  uint32_t* cursor;           // [G]
+  uint32_t* cursor;           // [G] (no kernel reads it any more; kept: the argument block's layout)
   uint2* items;
   // ggate == null (K1F listed the events, no gates pass ran): a file's group gates from its
   // keyword bits, as ggate_file computes them
@@ -1534,7 +1460,7 @@ struct ItemArgs {
   uint32_t W;
   const unsigned long long* kwg;
   const unsigned long long* galw;
-  unsigned long long* clk;  // K1FArgs::clk ([2]: the item passes' first block start)
+  unsigned long long* clk;  // K1FArgs::clk (kClkGatesStart: the item passes' first block start)
   uint32_t kwg_lds;         // kwg staged in the passes' LDS (its bytes; 0: read from global)
 };
 
@@ -1606,14 +1532,10 @@ struct GateArgs {
 // round trip per bit -- a file of a 1,000-rule set holds a hundred of them -- so the table
 // is staged in LDS when it fits)
 constexpr uint32_t kKwgLdsMax = 48 * 1024;
-#ifndef GATES_STAMPS
-#define GATES_STAMPS 8  // blocks that stamp the chain's start (measurement builds: more)
-#endif
 __global__ void __launch_bounds__(kBlock) gates_kernel(GateArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  // (the chain's start: the first blocks only -- blocks are dispatched in order, and ~850
-  // same-address atomics at the start of every block of the launch queue on one line)
-  if (threadIdx.x == 0 && blockIdx.x < GATES_STAMPS) atomicMax(&A.clk[2], ~(unsigned long long)wall_clock64());
+  if (threadIdx.x == 0 && blockIdx.x < kStampBlocks)  // (the chain's start)
+    atomicMax(&A.clk[kClkGatesStart], ~(unsigned long long)wall_clock64());
   if (blockIdx.x < A.ev_blocks) {
     ev_compact_block(A.ev, A.nchunks, A.evlist, A.nev, blockIdx.x, A.ev_blocks);
   } else {
@@ -1748,13 +1670,10 @@ __device__ __forceinline__ void gen_items(const ItemArgs& A, const ItemLds& T, u
 // Both item passes run a fixed grid over the work units t in [0, nev + F) (nev is read on
 // the device, so the host never waits for it), each block visiting the same units twice.
 // count pass: items per group (block totals in LDS, one global atomic per group and block)
-#ifndef ITEMS_BASE_IN_COUNT
-#define ITEMS_BASE_IN_COUNT 1  // (0: the emit pass reserves the block's ranges; measurement builds)
-#endif
 __global__ void __launch_bounds__(kBlock) items_count_kernel(ItemArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  if (!A.ggate && threadIdx.x == 0 && blockIdx.x < GATES_STAMPS)  // (no gates pass)
-    atomicMax(&A.clk[2], ~(unsigned long long)wall_clock64());
+  if (!A.ggate && threadIdx.x == 0 && blockIdx.x < kStampBlocks)  // (no gates pass)
+    atomicMax(&A.clk[kClkGatesStart], ~(unsigned long long)wall_clock64());
   const ItemLds T = item_lds_load(A, smem);
   uint32_t* s_count = (uint32_t*)(smem + item_lds_bytes(A));
   for (uint32_t g = threadIdx.x; g < A.G; g += blockDim.x) s_count[g] = 0;
@@ -1765,14 +1684,8 @@ __global__ void __launch_bounds__(kBlock) items_count_kernel(ItemArgs A) {
   __syncthreads();
   // the block's place in each group's region, reserved here: the emit pass's blocks then
   // start without a returning atomic per group (those queued on the groups' cursors)
-  for (uint32_t g = threadIdx.x; g < A.G; g += blockDim.x) {
-#if ITEMS_BASE_IN_COUNT
+  for (uint32_t g = threadIdx.x; g < A.G; g += blockDim.x)
     A.bcount[(size_t)blockIdx.x * A.G + g] = s_count[g] ? atomicAdd(&A.count[g], s_count[g]) : 0u;
-#else
-    A.bcount[(size_t)blockIdx.x * A.G + g] = s_count[g];
-    if (s_count[g]) atomicAdd(&A.count[g], s_count[g]);
-#endif
-  }
 }
 
 // ---------------------------------------------------------------- device-side item layout
@@ -1798,19 +1711,15 @@ struct LayoutArgs {
   uint4* dentries;    // ... of dense groups: {group, first chunk, n, kGroupDense}
   uint32_t* ndentries;
   uint8_t* gskip;     // [G] (to the host)
-  uint32_t* stats;    // [1] items listed, [2] entries, [3] skipped groups
+  uint32_t* stats;    // the batch's counters at kCntLayout: [kLayItems], [kLayEntries], [kLaySkipped]
 };
 
-
-// K2's list kernel block (measurement builds vary it).  The stepping is bound by LDS bank
-// conflicts of the transition reads (random rows), so a CU's entries take the same time
+// K2's list kernel block.  The stepping is bound by LDS bank conflicts of the transition
+// reads (random rows), so a CU's entries take the same time
 // however its waves are grouped: 1,024-thread blocks (one DFA staged for 16 waves, 292
 // entries of 2,048 items in about one round) ran 0.141 ms against 0.132 for 256 threads
 // (972 entries of 512), profiles/r05/c6.
-#ifndef K2_LIST_BLOCK
-#define K2_LIST_BLOCK 256
-#endif
-constexpr int kK2Block = K2_LIST_BLOCK;
+constexpr int kK2Block = 256;
 constexpr uint32_t kEntryItems = 2 * kK2Block;  // two chains per lane
 constexpr uint32_t kEntryChunks = kStreams * kBlock;
 static_assert(kEntryItems == kK2EntryItems && kEntryChunks == kK2EntryChunks, "layout_reference restates these");
@@ -1930,9 +1839,9 @@ __device__ void layout_block(const LayoutArgs& A, uint8_t* s_kind, uint32_t* s_g
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     *A.nentries = (uint32_t)s_carry[1];
     *A.ndentries = (uint32_t)s_carry[4];
-    A.stats[1] = (uint32_t)min<unsigned long long>(s_carry[0], 0xFFFFFFFFull);
-    A.stats[2] = (uint32_t)s_carry[1];
-    A.stats[3] = (uint32_t)s_carry[3];
+    A.stats[kLayItems] = (uint32_t)min<unsigned long long>(s_carry[0], 0xFFFFFFFFull);
+    A.stats[kLayEntries] = (uint32_t)s_carry[1];
+    A.stats[kLaySkipped] = (uint32_t)s_carry[3];
   }
 }
 
@@ -1950,12 +1859,7 @@ __global__ void __launch_bounds__(kBlock) items_emit_kernel(ItemArgs A, LayoutAr
   const uint64_t nt = (uint64_t)min(*A.nev, A.evcap) + A.F, stride = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (uint32_t g = threadIdx.x; g < A.G; g += blockDim.x) {
-#if ITEMS_BASE_IN_COUNT
     s_base[g] = s_kind[g] == kGroupList ? s_gbase[g] + A.bcount[(size_t)blockIdx.x * A.G + g] : 0u;
-#else
-    const uint32_t n = s_kind[g] == kGroupList ? A.bcount[(size_t)blockIdx.x * A.G + g] : 0;
-    s_base[g] = n ? s_gbase[g] + atomicAdd(&A.cursor[g], n) : 0;
-#endif
     s_count[g] = 0;
   }
   __syncthreads();
@@ -1980,7 +1884,7 @@ struct K2Args {
   const uint32_t* gmask;    // [G * kw_words] keyword gate of each group (dense entries)
   const uint32_t* galways;  // [G]
   const uint2* items;       // list entries: (file, chunk)
-  const uint4* entries;     // list entries {group, first item, n, kind} (layout_kernel)
+  const uint4* entries;     // list entries {group, first item, n, kind} (layout_block)
   const uint32_t* nentries;
   const uint4* dentries;    // dense entries {group, first chunk, n, kind}
   const uint32_t* ndentries;
@@ -2037,16 +1941,6 @@ __device__ __forceinline__ void emit_cand(const K2Args& A, uint32_t file, uint32
   A.hascand[file] = 1;
 }
 
-#ifdef K2_NOINL  // the rare paths out of line (their registers do not add to the hot loop's)
-#define K2_NOINLINE __attribute__((noinline))
-#else
-#define K2_NOINLINE __forceinline__
-#endif
-#ifdef K2_W
-#define K2_WAVES __attribute__((amdgpu_waves_per_eu(K2_W, 8)))
-#else
-#define K2_WAVES
-#endif
 struct Lane {
   const DevDFA& d;
   const K2Args& A;
@@ -2096,7 +1990,7 @@ struct Lane {
   // run; emitting those one by one, each after a dependent global lookup of the accept
   // mask and the rules, made entries of a few dozen items the kernel's long pole
   // (profiles/r03/d2, r03/k2a: 30-80 items, ~600 candidates, 0.4-0.5 ms).
-  __device__ K2_NOINLINE void replay_emit(uint32_t s0, const uint4 v, int lo, int hi, uint64_t wb) {
+  __device__ __forceinline__ void replay_emit(uint32_t s0, const uint4 v, int lo, int hi, uint64_t wb) {
     uint32_t n = 0, r = s0;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -2148,7 +2042,7 @@ struct Lane {
   }
 
   // matches that started before b: follow them past b (noinject) until they all die
-  __device__ K2_NOINLINE void tail(uint32_t s, uint64_t fe, uint64_t b) {
+  __device__ __forceinline__ void tail(uint32_t s, uint64_t fe, uint64_t b) {
     if (b >= fe) {
       const uint32_t m = d.eot[state_of(s)];
       if (m) emit(m, fe);
@@ -2157,7 +2051,7 @@ struct Lane {
     tail_ni(d.to_ni[state_of(s)], fe, b);
   }
   // the same from the noinject row already looked up (s = to_ni of the chain's row, b < fe)
-  __device__ K2_NOINLINE void tail_ni(uint32_t s, uint64_t fe, uint64_t b) {
+  __device__ __forceinline__ void tail_ni(uint32_t s, uint64_t fe, uint64_t b) {
     const uint8_t* data = A.data;
     const uint8_t* dead = s_cls + (d.o_dead - d.o_cls);  // (staged: stage_dfa)
     // 16 bytes per load (the next word in flight), liveness checked once per word: a dead
@@ -2588,7 +2482,7 @@ __device__ __forceinline__ void k2_run(const DevDFA* __restrict__ dfas, const K2
 #endif
     prev = e;
     if (e >= E) {
-      if (ran && threadIdx.x == 0) atomicMax(&A.clk[3], (unsigned long long)wall_clock64());
+      if (ran && threadIdx.x == 0) atomicMax(&A.clk[kClkK2End], (unsigned long long)wall_clock64());
       break;
     }
     ran = true;
@@ -2608,7 +2502,7 @@ __device__ __forceinline__ void k2_run(const DevDFA* __restrict__ dfas, const K2
   }
 }
 
-__global__ void __launch_bounds__(kK2Block) K2_WAVES k2_kernel(const DevDFA* __restrict__ dfas, K2Args A) {
+__global__ void __launch_bounds__(kK2Block) k2_kernel(const DevDFA* __restrict__ dfas, K2Args A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   k2_run<false>(dfas, A, A.entries, *A.nentries, A.claim, smem);
 }
@@ -2745,15 +2639,7 @@ static int k1_lds_class(size_t tab_bytes) {
 }
 
 // the packed layout holds rows as 16-bit byte offsets: ns * stride u16 entries in 64 KiB
-static bool k1_packed_fits(size_t ns, size_t rs) {
-#ifdef K1_LEGACY  // measurement builds: the legacy layout for every automaton
-  (void)ns;
-  (void)rs;
-  return false;
-#else
-  return ns * rs * 2 <= 65536;
-#endif
-}
+static bool k1_packed_fits(size_t ns, size_t rs) { return ns * rs * 2 <= 65536; }
 
 // Row stride (u16 entries) of the K1 table: the class count padded to 2 mod 4, so a row is
 // an odd number of dwords and equal classes of different rows fall in different LDS banks
@@ -3030,7 +2916,7 @@ struct LaneState {
   size_t dentries_cap = 0;
   DevCand* cand = nullptr;
   uint32_t cand_cap = 0;
-  uint32_t* counts = nullptr;   // [16] 0 candidates, 1 event chunks, 2 K2 entries, ...
+  uint32_t* counts = nullptr;   // [kCounts] the batch's counter block (CountSlot, device.hpp)
   uint32_t* gcount = nullptr;   // [G]
   uint32_t* bcount = nullptr;   // [grid * G] items_count_kernel's per-block counts
   uint32_t* cursor = nullptr;   // [G]
@@ -3248,7 +3134,7 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
   K1FArgs A = A0;
   A.ntiles = std::min<uint32_t>(A0.ntiles, (16u << 20) / kFTile);
   A.hits = r->d_fhits;
-  A.stats = l->counts + 24;  // (the batch's own counters stay those of its real launch)
+  A.stats = l->counts + kCntK1FSample;  // (the batch's own counters stay those of its real launch)
   A.clk = nullptr;
   A.evlist = nullptr;
   A.nev = nullptr;
@@ -3444,11 +3330,6 @@ int lane_create(DeviceRules* d, LaneState** out) {
   l->d = d;
   HIP_TRY(hipStreamCreateWithFlags(&l->st, hipStreamNonBlocking));
   const uint32_t G = std::max<uint32_t>(1, (uint32_t)d->groups.size());
-  // per-batch counters: 0 candidates, 1 event chunks, 2 K2 entries, 3 dense entries, 5-7
-  // layout (5 items, 6 entries, 7 groups skipped), 8-11 K2 diagnostics,
-  // 12-13 K2 claim cursors (list, dense), 14-15 K1X (records listed, inline verified),
-  // 16-17 K1F (words listed, literal occurrences verified), 24-25 the same of the
-  // adaptation's sampling launch
   HIP_TRY(hipMalloc((void**)&l->counts, sizeof(uint32_t) * kCounts));
   HIP_TRY(hipMalloc((void**)&l->gcount, sizeof(uint32_t) * G));
   HIP_TRY(hipMalloc((void**)&l->bcount, sizeof(uint32_t) * G * (size_t)d->grid));
@@ -3643,12 +3524,12 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   const bool k1f_list = k1f && total && !r->has_k1x && knobs().k1f_list.load() && k1f_lists(r, k1f_tiles, C);
   if (k1f) {
     K1FArgs A{data, l->off, l->cf, (uint32_t)total, C, F, k1f_tiles, F ? (uint32_t)ncf : 0u,
-              l->kw, l->ev_bits, nullptr, l->counts + 16, (unsigned long long*)(l->counts + kClk),
+              l->kw, l->ev_bits, nullptr, l->counts + kCntK1F, (unsigned long long*)(l->counts + kCntClk),
               nullptr, nullptr, r->k1f_maxlen, 0, nullptr, nullptr};
     if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.data))) return rc;
     if (k1f_list) {
       A.evlist = l->evlist;
-      A.nev = l->counts + 1;
+      A.nev = l->counts + kCntEvChunks;
       A.evcap = (uint32_t)std::min<size_t>(l->evlist_cap, 0xFFFFFFFFu);
       A.zone = r->k1f_maxlen;  // (after the adaptation's rebuild)
       A.claim = l->zclaim;
@@ -3673,7 +3554,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     const int xg = (int)std::max<uint64_t>(1, std::min<uint64_t>((total / 16 + kK1XBlock - 1) / kK1XBlock,
                                                                    (uint64_t)r->cus));
     K1XArgs X{data, l->off, l->cf, total, C, F, l->kw, l->ev_bits, l->xlist, l->xcount,
-              (uint32_t)std::min<size_t>(l->xlist_cap, 0xFFFFFFFFu), l->counts + 14};
+              (uint32_t)std::min<size_t>(l->xlist_cap, 0xFFFFFFFFu), l->counts + kCntK1X};
     void* xa[] = {(void*)&r->k1x, (void*)&X};
     HIP_TRY(hipLaunchKernel(k1x_fn(r->k1x.step), dim3(xg), dim3(kK1XBlock), xa, kXDwords * 4 + 16, st));
     if (r->k1x.img_bytes <= kXImgLds)
@@ -3703,35 +3584,35 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   IA.bcount = l->bcount;
   IA.cursor = l->cursor;
   IA.evlist = l->evlist;
-  IA.nev = l->counts + 1;
+  IA.nev = l->counts + kCntEvChunks;
   IA.evcap = (uint32_t)std::min<size_t>(l->evlist_cap, 0xFFFFFFFFu);
   IA.items = l->items;
   IA.kw = l->kw;
   IA.W = W;
   IA.kwg = r->d_kwg;
   IA.galw = r->d_galw;
-  IA.clk = (unsigned long long*)(l->counts + kClk);
+  IA.clk = (unsigned long long*)(l->counts + kCntClk);
   const bool work = F && G && nchunks;
   if (work && k1f_list) {
     IA.ggate = nullptr;  // (files gated from their keyword bits in the item passes)
   } else if (work) {
     const uint32_t cgrid = (uint32_t)std::min<uint64_t>((nchunks + kEvPer * kBlock - 1) / (kEvPer * kBlock), (uint64_t)r->grid);
     const uint32_t kwg_bytes = (uint32_t)(32ull * W * r->GW * 8);
-    GateArgs GA{l->ev_bits, nchunks, l->evlist, l->counts + 1, cgrid, l->kw, F, W, r->GW, r->d_kwg, r->d_galw, l->ggate,
-                (unsigned long long*)(l->counts + kClk), kwg_bytes <= kKwgLdsMax ? kwg_bytes : 0u};
+    GateArgs GA{l->ev_bits, nchunks, l->evlist, l->counts + kCntEvChunks, cgrid, l->kw, F, W, r->GW, r->d_kwg, r->d_galw, l->ggate,
+                (unsigned long long*)(l->counts + kCntClk), kwg_bytes <= kKwgLdsMax ? kwg_bytes : 0u};
     gates_kernel<<<cgrid + (F + kBlock - 1) / kBlock, kBlock, GA.kwg_lds, st>>>(GA);
     HIP_TRY(hipGetLastError());
   }
   if (work) {
-    // both items passes (bcount holds grid x G); ITEMS_BPC blocks per CU
-    const int igrid = std::min(r->grid, r->cus * ITEMS_BPC);
+    // both items passes (bcount holds grid x G); kItemsBpc blocks per CU
+    const int igrid = std::min(r->grid, r->cus * kItemsBpc);
     const uint32_t kwg_bytes = (uint32_t)(32ull * W * r->GW * 8);
     IA.kwg_lds = !IA.ggate && kwg_bytes <= kItemKwgLdsMax ? kwg_bytes : 0u;
     const size_t ilds = item_lds_host(G, r->GW) + IA.kwg_lds;
     hipLaunchKernelGGL(items_count_kernel, dim3(igrid), dim3(kBlock), ilds + G * sizeof(uint32_t) + 16, st, IA);
     HIP_TRY(hipGetLastError());
-    LayoutArgs LA{l->gcount, G, nchunks, items_cap, max_dense, l->entries, l->counts + 2,
-                  l->dentries, l->counts + 3, l->gskip, l->counts + 4};
+    LayoutArgs LA{l->gcount, G, nchunks, items_cap, max_dense, l->entries, l->counts + kCntListEntries,
+                  l->dentries, l->counts + kCntDenseEntries, l->gskip, l->counts + kCntLayout};
     hipLaunchKernelGGL(items_emit_kernel, dim3(igrid), dim3(kBlock), ilds + 3 * G * sizeof(uint32_t) + G + 16, st, IA, LA);
     HIP_TRY(hipGetLastError());
   }
@@ -3754,23 +3635,23 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     A.galways = r->d_galways;
     A.items = l->items;
     A.entries = l->entries;
-    A.nentries = l->counts + 2;
+    A.nentries = l->counts + kCntListEntries;
     A.dentries = l->dentries;
-    A.ndentries = l->counts + 3;
+    A.ndentries = l->counts + kCntDenseEntries;
     A.cand = l->cand;
-    A.cand_count = l->counts;
+    A.cand_count = l->counts + kCntCand;
     A.cand_cap = out->cand_cap;
     A.ovf = l->ovf;
     A.hascand = l->hascand;
     static const bool diag = getenv("TSG_K2_DIAG") != nullptr;
-    A.diag = diag ? l->counts + 8 : nullptr;
-    A.claim = l->counts + 12;
+    A.diag = diag ? l->counts + kCntK2Diag : nullptr;
+    A.claim = l->counts + kCntK2Claim;
     A.word_recs = G <= 0x3FFF && !knobs().k2_no_word_recs.load();
     static const bool trace = getenv("TSG_K2_TRACE") != nullptr;
     if (trace && (rc = ensure(&l->etrace, &l->etrace_cap, (size_t)entries_cap * kTraceW))) return rc;
     if (trace) HIP_TRY(hipMemsetAsync(l->etrace, 0, sizeof(unsigned long long) * entries_cap * kTraceW, st));
     A.etrace = trace ? l->etrace : nullptr;
-    A.clk = (unsigned long long*)(l->counts + kClk);
+    A.clk = (unsigned long long*)(l->counts + kCntClk);
     // one block per resident slot (the grids are persistent)
     if (r->k2_rich)
       hipLaunchKernelGGL(k2_kernel_rich, dim3(r->k2_grid), dim3(kK2Block), r->max_lds, st, (const DevDFA*)r->d_groups, A);
@@ -3831,14 +3712,14 @@ int batch_times(const HostOut* o, ScanTimes* t) {
   t->gates = x[5];
   t->k2 = x[6];
   t->out = x[7];
-  // the kernels' own spans by the device wall clock (stamps in counts + kClk; 0 if a
-  // kernel did not run)
-  const unsigned long long* c = (const unsigned long long*)(o->counts + kClk);
+  // the kernels' own spans by the device wall clock (ClkStamp; 0 if a kernel did not run;
+  // a start is stored as its complement)
+  const unsigned long long* c = (const unsigned long long*)(o->counts + kCntClk);
   const double per_ms = o->wall_khz ? (double)o->wall_khz : 100000.0;
-  const unsigned long long k1s = ~c[0], k1e = c[1], k2e = c[3];
-  t->k1_clk = c[0] && k1e > k1s ? (float)((k1e - k1s) / per_ms) : 0.f;
-  t->chain_clk = c[0] && k2e > k1s ? (float)((k2e - k1s) / per_ms) : 0.f;
-  t->post_k1_clk = c[2] && k2e > ~c[2] ? (float)((k2e - ~c[2]) / per_ms) : 0.f;
+  const unsigned long long k1s = ~c[kClkK1FStart], k1e = c[kClkK1FEnd], gs = ~c[kClkGatesStart], k2e = c[kClkK2End];
+  t->k1_clk = c[kClkK1FStart] && k1e > k1s ? (float)((k1e - k1s) / per_ms) : 0.f;
+  t->chain_clk = c[kClkK1FStart] && k2e > k1s ? (float)((k2e - k1s) / per_ms) : 0.f;
+  t->post_k1_clk = c[kClkGatesStart] && k2e > gs ? (float)((k2e - gs) / per_ms) : 0.f;
   return TSG_OK;
 }
 
@@ -3847,9 +3728,9 @@ int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out) {
   HIP_TRY(hipStreamSynchronize(l->st));
   out->clear();
   if (!l->etrace) return TSG_OK;
-  uint32_t counts[16];
-  HIP_TRY(hipMemcpy(counts, l->counts, sizeof(counts), hipMemcpyDeviceToHost));
-  const size_t n = std::min<size_t>((size_t)counts[2] * kTraceW, l->etrace_cap);
+  uint32_t nent = 0;
+  HIP_TRY(hipMemcpy(&nent, l->counts + kCntListEntries, sizeof(nent), hipMemcpyDeviceToHost));
+  const size_t n = std::min<size_t>((size_t)nent * kTraceW, l->etrace_cap);
   out->resize(n);
   if (n) HIP_TRY(hipMemcpy(out->data(), l->etrace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return TSG_OK;
@@ -3873,16 +3754,18 @@ int lane_kw(LaneState* l, uint32_t* kw, size_t n) {
 int lane_items(LaneState* l, LaneItems* out) {
   HIP_TRY(hipSetDevice(l->d->device));
   HIP_TRY(hipStreamSynchronize(l->st));
-  uint32_t counts[8];
-  HIP_TRY(hipMemcpy(counts, l->counts, sizeof(counts), hipMemcpyDeviceToHost));
+  uint32_t nent = 0, ndent = 0, nitems = 0;
+  HIP_TRY(hipMemcpy(&nent, l->counts + kCntListEntries, sizeof(nent), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&ndent, l->counts + kCntDenseEntries, sizeof(ndent), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&nitems, l->counts + kCntItems, sizeof(nitems), hipMemcpyDeviceToHost));
   // (the counters are the layout's; the buffers' own sizes bound every copy)
-  const size_t ne = std::min<size_t>(counts[2], l->entries_cap), nd = std::min<size_t>(counts[3], l->dentries_cap),
-               ni = std::min<size_t>(counts[5], l->items_cap), G = l->d->groups.size();
+  const size_t ne = std::min<size_t>(nent, l->entries_cap), nd = std::min<size_t>(ndent, l->dentries_cap),
+               ni = std::min<size_t>(nitems, l->items_cap), G = l->d->groups.size();
   out->entries.assign(4 * ne, 0);
   out->dentries.assign(4 * nd, 0);
   out->items.assign(2 * ni, 0);
   out->gskip.assign(G, 0);
-  out->extent = counts[5];
+  out->extent = nitems;
   if (ne) HIP_TRY(hipMemcpy(out->entries.data(), l->entries, sizeof(uint4) * ne, hipMemcpyDeviceToHost));
   if (nd) HIP_TRY(hipMemcpy(out->dentries.data(), l->dentries, sizeof(uint4) * nd, hipMemcpyDeviceToHost));
   if (ni) HIP_TRY(hipMemcpy(out->items.data(), l->items, sizeof(uint2) * ni, hipMemcpyDeviceToHost));

@@ -93,7 +93,7 @@ struct Batch {
   std::unique_ptr<tsg_result> res;
   BatchResult br;
   ScanTimes t;
-  uint32_t counts[48] = {};
+  uint32_t counts[kCounts] = {};  // the device's counter block, or its emulation (CountSlot)
   uint32_t cand_cap = 0;  // candidate records the kernels (or their emulation) had room for
   double resolve_ms = 0;
   uint64_t files_found = 0;
@@ -300,31 +300,31 @@ void update_stats(tsg_ctx* c, const Batch& b) {
   s.meta_ms = b.t.meta;
   s.resolve_ms = b.resolve_ms;
   s.bytes = b.bytes;
-  s.candidates = b.counts[0];
-  s.overflow = b.counts[0] > b.cand_cap ? 1 : 0;
-  s.k2_dense_entries = b.counts[3];
+  s.candidates = b.counts[kCntCand];
+  s.overflow = b.counts[kCntCand] > b.cand_cap ? 1 : 0;
+  s.k2_dense_entries = b.counts[kCntDenseEntries];
   s.k2_rich = c->dr && device_rules_k2_rich(c->dr) ? 1u : 0u;
-  s.k2_items = b.counts[5];
-  s.k2_bytes = (uint64_t)b.counts[5] * c->opt.chunk_bytes;
-  s.k2_launches = b.counts[6];
-  s.groups_skipped = b.counts[7];
+  s.k2_items = b.counts[kCntItems];
+  s.k2_bytes = (uint64_t)b.counts[kCntItems] * c->opt.chunk_bytes;
+  s.k2_launches = b.counts[kCntEntries];
+  s.groups_skipped = b.counts[kCntSkipped];
   s.files_resolved = b.files_found;
   s.wait_ms = b.t.wait;
-  s.k2_tail_bytes = b.counts[8];
-  s.k2_tail_max = b.counts[9];
-  s.k2_long_tails = b.counts[10];
-  s.k2_replays = b.counts[11];
-  s.k1x_records = b.counts[14];
-  s.k1x_inline = b.counts[15];
-  s.k1f_listed = b.counts[16];
-  s.k1f_arrivals = b.counts[17];
+  s.k2_tail_bytes = b.counts[kCntK2Diag];
+  s.k2_tail_max = b.counts[kCntK2Diag + 1];
+  s.k2_long_tails = b.counts[kCntK2Diag + 2];
+  s.k2_replays = b.counts[kCntK2Diag + 3];
+  s.k1x_records = b.counts[kCntK1X];
+  s.k1x_inline = b.counts[kCntK1X + 1];
+  s.k1f_listed = b.counts[kCntK1F];
+  s.k1f_arrivals = b.counts[kCntK1F + 1];
   s.k1_clock_ms = b.t.k1_clk;
   s.chain_clock_ms = b.t.chain_clk;
   s.post_k1_clock_ms = b.t.post_k1_clk;
   s.sum_k1_clock_ms += b.t.k1_clk;
   s.sum_chain_clock_ms += b.t.chain_clk;
   s.sum_post_k1_clock_ms += b.t.post_k1_clk;
-  s.event_chunks = b.counts[1];
+  s.event_chunks = b.counts[kCntEvChunks];
   s.k1_filter = c->dr && device_rules_k1_filter(c->dr) && b.bytes + (1u << 16) < (1ull << 32) ? 1u : 0u;
   s.k1_hot_states = c->dr ? device_rules_hot_states(c->dr) : 0;
   s.batches++;
@@ -359,25 +359,20 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       emulate_kernels(*rs->plan, view, c->opt.chunk_bytes, c->opt.ext_cap, &emu, nullptr, &eo, &es);
       kv = emu.view();
       auto u32 = [](uint64_t x) { return (uint32_t)std::min<uint64_t>(x, 0xFFFFFFFFu); };
-      b->counts[0] = u32(es.candidates);
-      b->counts[3] = u32(es.layout.dense_entries);
-      b->counts[5] = u32(es.layout.extent);
-      b->counts[6] = u32(es.layout.entries);
-      b->counts[7] = u32(es.layout.skipped);
+      b->counts[kCntCand] = u32(es.candidates);
+      b->counts[kCntDenseEntries] = u32(es.layout.dense_entries);
+      b->counts[kCntItems] = u32(es.layout.extent);
+      b->counts[kCntEntries] = u32(es.layout.entries);
+      b->counts[kCntSkipped] = u32(es.layout.skipped);
       b->cand_cap = c->opt.cand_capacity;
     } else {
       if (hipEventSynchronize(ho.ev[kEvDone]) != hipSuccess) throw std::runtime_error("device batch failed");
       (void)batch_times(&ho, &b->t);
       std::memcpy(b->counts, ho.counts, sizeof(b->counts));
-      // counts from the device: 0 candidates, 1 event chunks, 2 K2 entries; layout stats
-      // 4+1 items, 4+2 entries, 4+3 skipped groups
-      const uint32_t items = ho.counts[5], entries = ho.counts[6], skipped = ho.counts[7];
-      b->counts[5] = items;
-      b->counts[6] = entries;
-      b->counts[7] = skipped;
+      const uint32_t skipped = ho.counts[kCntSkipped];  // (slots: CountSlot, device.hpp)
       kv.kw = ho.kw;
       kv.cand = ho.cand;
-      kv.ncand = std::min<uint32_t>(ho.counts[0], ho.cand_cap);
+      kv.ncand = std::min<uint32_t>(ho.counts[kCntCand], ho.cand_cap);
       b->cand_cap = ho.cand_cap;
       kv.overflow = ho.ovf;
       kv.sparse_kw = true;  // outputs_kernel: flags and the keyword rows the host reads
