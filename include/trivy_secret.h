@@ -14,6 +14,8 @@
  *       scanner.go:55-57 (used by SecretAnalyzer.Required, analyzer/secret/secret.go:145)
  *   (*Scanner).Scan(ScanArgs) types.Secret            tsg_scan_cpu (one file, exact CPU)
  *       scanner.go:341-416                            tsg_scan_batch (many files, GPU)
+ *                                                     tsg_scan_device (many files already
+ *                                                       in this GPU's memory)
  *   SecretAnalyzer.Analyze per-file goroutines        tsg_queue_scan (concurrent callers
  *       analyzer/secret/secret.go:78-110,               coalesced into pinned batches),
  *       analyzer.go:419-443                             tsg_slot_* / tsg_scan_batch (batches)
@@ -25,7 +27,8 @@
  * exception crosses the ABI.  Every entry point is thread-safe (the GPU calls name the
  * caller's own slot and submission ticket; none acts on "the last" batch); a tsg_ruleset
  * is immutable and may be shared by any number of threads and contexts.  The library never
- * retains a caller pointer past a call.
+ * retains a caller pointer past a call, with one documented exception: the device buffer of
+ * tsg_device_submit, which the caller leaves untouched until the ticket is collected.
  *
  * Result format (tsg_result_data), little endian:
  *   u32 magic 'TSG1' (0x31475354), u32 nfiles, then per file:
@@ -138,7 +141,8 @@ int tsg_result_summary(const tsg_result* r, uint64_t* nfiles, uint64_t* files_wi
  * H2D of one batch overlaps the kernels of the other), a pool of pinned host slots that
  * batches are staged in, and the host resolvers of batches in flight.  The library never
  * retains a caller pointer past a call (batch bytes are copied into, or written directly
- * by the caller into, library-owned pinned slots).
+ * by the caller into, library-owned pinned slots); the device-resident input below is the
+ * exception and says so.
  *
  * Threading: every entry point below is thread-safe on a shared context.  No call acts on
  * "the last" anything: a caller names its own slot (slot id) and its own submission
@@ -289,6 +293,47 @@ typedef struct tsg_stats {
 } tsg_stats;
 int tsg_ctx_get_stats(const tsg_ctx* ctx, tsg_stats* out);
 
+/* -- Device-resident input: the batch's bytes already live in this device's HBM ---------
+ * (a torch tensor, the output of a GPU decompressor).  d_data is a device pointer on the
+ * context's device, at any byte alignment, covering offsets[nfiles] bytes that are written
+ * when the call is made; offsets, paths and path_offsets are host arrays as for
+ * tsg_scan_batch.  No content crosses PCIe in bulk: a kernel stages the bytes into the
+ * lane's buffer (HBM -> HBM, one extra read and write of the batch), every scan kernel runs
+ * unchanged, and after them only the files the host resolver reads (files with a candidate,
+ * empty files, flagged files) are copied device -> host into a pinned slot that mirrors the
+ * batch sparsely; when every file is needed (rules without a GPU program, a skipped rule
+ * group) the whole batch is copied in one D2H instead.  The slot is as large as the batch.
+ * The caller leaves d_data untouched until the ticket is collected (tsg_batch_collect);
+ * tsg_scan_device is submit + collect.  Results are byte-identical to tsg_scan_batch's for
+ * the same bytes on the same context.  TSG_ERR_ARG: NULL context, NULL d_data with a
+ * non-empty batch, offsets that do not start at 0 or decrease.  Under TSG_CTX_EMULATE
+ * d_data is an ordinary host pointer (nothing is staged; the fetch is a memcpy of the same
+ * segments). */
+int tsg_device_submit(tsg_ctx* ctx, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                      const char* paths, const uint64_t* path_offsets, uint64_t* ticket);
+int tsg_scan_device(tsg_ctx* ctx, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                    const char* paths, const uint64_t* path_offsets, tsg_result** out);
+typedef struct tsg_device_input_stats {
+  /* last collected device-resident batch */
+  double stage_ms;         /* the staging kernel (HIP events; also tsg_stats.h2d_ms); 0 emulated */
+  double fetch_ms;         /* the fetch: kernel or D2H by HIP events (wall time when emulated) */
+  uint64_t fetched_files;  /* files the host resolver reads (empty ones included) */
+  uint64_t fetched_bytes;  /* their bytes: what crossed PCIe */
+  /* all device-resident batches so far */
+  uint64_t batches, sum_bytes, sum_fetched_bytes;
+  double sum_stage_ms, sum_fetch_ms;
+  uint32_t whole_batch_copy; /* last batch: 1 = every file was needed, one D2H of the batch */
+} tsg_device_input_stats;
+int tsg_ctx_get_device_input_stats(const tsg_ctx* ctx, tsg_device_input_stats* out);
+/* Test hook: the pinned mirror of the last finished device-resident batch as its fetch left
+ * it (TSG_ERR_ARG if there was none, or if its slot has been handed out again since: any
+ * later batch may take it).  n[0] = the batch's
+ * bytes, n[1] = fetched segments; up to data_cap mirror bytes and up to segs_cap segments
+ * {offset, length} (2 u64 each, ascending, disjoint) are copied (either pointer may be
+ * NULL). */
+int tsg_test_device_mirror(tsg_ctx* ctx, uint8_t* data, uint64_t data_cap, uint64_t* segs,
+                           size_t segs_cap, uint64_t* n);
+
 /* -- Submission queue for concurrent per-file callers ----------------------------------
  * The analyzer framework calls Analyze -> Scan from one goroutine per file
  * (pkg/fanal/analyzer/analyzer.go:419-443).  tsg_queue_scan is that Scan: any number of
@@ -360,6 +405,10 @@ const char* tsg_last_error(void);
  *   "k2_no_word_recs" "1": K2 writes a record per accepting transition instead of one per
  *                     accepting 16-B word, as for rule sets of 16,384 groups and more (the
  *                     emulation then ignores emu_wordrec)
+ *   "device_poison"   "1": tsg_device_submit fills the batch's pinned mirror, before the
+ *                     fetch, with a repeating line that the builtin rules match (an AWS access
+ *                     key id): a resolver read of a byte that was not fetched shows up as a
+ *                     wrong finding
  * Returns TSG_ERR_ARG for an unknown name. */
 int tsg_test_knob(const char* name, const char* value);
 

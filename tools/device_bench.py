@@ -1,0 +1,173 @@
+#!/usr/bin/env python
+"""Device-resident input against the PCIe path, same bytes, same context.
+
+    python tools/device_bench.py [--gb 4] [--steps 20] [--rounds 3] [--warmup 1] [--depth 4]
+
+The configs[1] workload of bench.py (builtin rules over the seeded corpus, seed 2, in
+batches of --batch-mib) is scanned two ways on one GpuContext:
+
+  pcie      the batches sit in pinned slots and are submitted with tsg_slot_submit, --depth
+            in flight: bench.py's headline path (content crosses PCIe once per scan)
+  resident  the same bytes were uploaded once as torch tensors and are submitted with
+            tsg_device_submit (GpuContext.submit_tensor), --depth in flight: staged HBM ->
+            HBM, and only the files the resolver reads come back
+
+Every batch's result bytes of the two paths are compared (they must be equal).  Prints one
+JSON line: GB/s of both paths, the per-batch stage / fetch / resolve / K1 times of the
+resident path, and the share of the bytes that was fetched.  The two paths are timed in
+alternation, --rounds windows of --steps passes each after --warmup passes, with the host
+clock over whole windows (every result collected); the line carries every window's GB/s
+and the medians.  The per-stage figures are the library's HIP-event times of the last
+window (tsg_stats, tsg_device_input_stats)."""
+import argparse
+import collections
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=4.0, help="GiB of corpus")
+    ap.add_argument("--batch-mib", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=20, help="passes over the corpus per timed window")
+    ap.add_argument("--rounds", type=int, default=3, help="timed windows per path, alternating")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--depth", type=int, default=4, help="batches in flight")
+    ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--emulate", action="store_true",
+                    help="dry run of this script without a GPU (emulated context, host tensors)")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from bench import fill_slots
+    from trivy_amd import _native as N
+    from trivy_amd import corpus
+    from trivy_amd import secret as S
+
+    def log(msg):
+        print(msg, file=sys.stderr, flush=True)
+
+    L = N.lib()
+    sc = S.NewScanner(None)
+    t0 = time.perf_counter()
+    batch, info = corpus.make_corpus(int(args.gb * (1 << 30)), seed=args.seed, plants_per_mib=1.0)
+    log("corpus %.2f GiB, %d files, generated in %.1fs" % (info["bytes"] / (1 << 30), info["files"],
+                                                          time.perf_counter() - t0))
+    nb = -(-int(batch.offsets[-1]) // (args.batch_mib << 20))
+    # pinned slots: the PCIe path's own, and one mirror per resident batch in flight
+    ctx = S.GpuContext(sc, args.device, max_slots=nb + args.depth + 4, emulate=args.emulate)
+    slots = fill_slots(ctx, batch, args.batch_mib << 20)
+    dev = "cpu" if args.emulate else "cuda:%d" % args.device
+    pieces, f0 = [], 0
+    for sid, nf, nbytes in slots:  # the same cuts, as tensors in HBM (uploaded once)
+        base = int(batch.offsets[f0])
+        offs = (batch.offsets[f0:f0 + nf + 1] - np.uint64(base)).copy()
+        t = torch.from_numpy(batch.data[base:base + nbytes]).to(dev)
+        # checked and packed once (submit_tensor would encode the paths again on every call)
+        pieces.append((t, ctx._tensor_args(t, offs, [batch.path(i) for i in range(f0, f0 + nf)])))
+        f0 += nf
+    if not args.emulate:
+        torch.cuda.synchronize()
+    total = sum(nbytes for _, _, nbytes in slots)
+    log("%d batches packed: pinned slots and device tensors" % len(slots))
+
+    def raw(out):
+        n = C.c_size_t()
+        p = L.tsg_result_data(out, C.byref(n))
+        buf = C.string_at(p, n.value)
+        L.tsg_result_free(out)
+        return buf
+
+    def run(submit, steps, keep):
+        """`steps` passes over the batches, --depth in flight; the last pass's result bytes
+        per batch when keep."""
+        q, kept = collections.deque(), {}
+
+        def collect():
+            t, k, i = q.popleft()
+            out = C.c_void_p()
+            N.check(L.tsg_batch_collect(ctx.handle, t, C.byref(out)))
+            if keep and k == steps - 1:
+                kept[i] = raw(out)
+            else:
+                L.tsg_result_free(out)
+
+        for k in range(steps):
+            for i in range(len(slots)):
+                q.append((submit(i), k, i))
+                while len(q) >= args.depth:
+                    collect()
+        while q:
+            collect()
+        return kept
+
+    def submit_pcie(i):
+        t = C.c_uint64()
+        N.check(L.tsg_slot_submit(ctx.handle, slots[i][0], slots[i][1], C.byref(t)))
+        return t.value
+
+    def submit_resident(i):
+        tk = C.c_uint64()
+        N.check(L.tsg_device_submit(ctx.handle, *pieces[i][1][0], C.byref(tk)))
+        return tk.value
+
+    def timed(submit):
+        run(submit, args.warmup, False)
+        s0, d0 = ctx.stats(), ctx.device_input_stats()
+        t0 = time.perf_counter()
+        kept = run(submit, args.steps, True)
+        dt = time.perf_counter() - t0
+        s1, d1 = ctx.stats(), ctx.device_input_stats()
+        ds = {k: s1[k] - s0[k] for k in s1 if k.startswith("sum_") or k == "batches"}
+        dd = {k: d1[k] - d0[k] for k in d1 if k.startswith("sum_") or k == "batches"}
+        return kept, dt, ds, dd
+
+    pgbs, rgbs, equal = [], [], True
+    for _ in range(max(1, args.rounds)):
+        pk, pdt, ps, _ = timed(submit_pcie)
+        rk, rdt, rs, rd = timed(submit_resident)
+        equal = equal and all(pk[i] == rk[i] for i in range(len(slots)))
+        pgbs.append(round(total * args.steps / pdt / 1e9, 3))
+        rgbs.append(round(total * args.steps / rdt / 1e9, 3))
+    nbat = max(1, rs["batches"])
+    pbat = max(1, ps["batches"])
+    line = {
+        "metric": "secret-scan GB/s (builtin rules), device-resident input vs the PCIe path, 1 MI355X",
+        "resident_gbs": round(float(np.median(rgbs)), 3),
+        "pcie_gbs": round(float(np.median(pgbs)), 3),
+        "unit": "GB/s",
+        "resident_gbs_windows": rgbs, "pcie_gbs_windows": pgbs,
+        "findings_equal": equal,
+        "gib": round(total / (1 << 30), 3), "batches": len(slots), "batch_mib": args.batch_mib,
+        "steps": args.steps, "rounds": args.rounds, "warmup": args.warmup, "depth": args.depth,
+        "resident_per_batch_ms": {
+            "stage": round(rs["sum_h2d_ms"] / nbat, 3), "fetch": round(rd["sum_fetch_ms"] / nbat, 3),
+            "k1": round(rs["sum_k1_ms"] / nbat, 3), "gates": round(rs["sum_gate_ms"] / nbat, 3),
+            "k2": round(rs["sum_k2_ms"] / nbat, 3), "resolve": round(rs["sum_resolve_ms"] / nbat, 3),
+            "wall": round(rdt / args.steps / len(slots) * 1e3, 3)},
+        "pcie_per_batch_ms": {
+            "h2d": round(ps["sum_h2d_ms"] / pbat, 3), "k1": round(ps["sum_k1_ms"] / pbat, 3),
+            "resolve": round(ps["sum_resolve_ms"] / pbat, 3),
+            "wall": round(pdt / args.steps / len(slots) * 1e3, 3)},
+        "fetched_share": round(rd["sum_fetched_bytes"] / max(1, rd["sum_bytes"]), 5),
+        "fetched_mib_per_batch": round(rd["sum_fetched_bytes"] / nbat / (1 << 20), 3),
+        "whole_batch_copy": ctx.device_input_stats()["whole_batch_copy"],
+    }
+    for sid, _, _ in slots:
+        ctx.release_slot(sid)
+    ctx.close()
+    print(json.dumps(line))
+    return 0 if equal else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -91,6 +91,15 @@ class Stats(C.Structure):
                 ("k2_dense_entries", C.c_uint32), ("k2_rich", C.c_uint32)]
 
 
+class DeviceInputStats(C.Structure):
+    """tsg_device_input_stats, in the header's order."""
+    _fields_ = [("stage_ms", C.c_double), ("fetch_ms", C.c_double),
+                ("fetched_files", C.c_uint64), ("fetched_bytes", C.c_uint64),
+                ("batches", C.c_uint64), ("sum_bytes", C.c_uint64),
+                ("sum_fetched_bytes", C.c_uint64), ("sum_stage_ms", C.c_double),
+                ("sum_fetch_ms", C.c_double), ("whole_batch_copy", C.c_uint32)]
+
+
 # (name, restype, argtypes) -- every symbol include/trivy_secret.h declares
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
@@ -121,6 +130,10 @@ SIGNATURES = [
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),
     ("tsg_ctx_get_stats", C.c_int, [_P, C.POINTER(Stats)]),
+    ("tsg_device_submit", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, _U64P]),
+    ("tsg_scan_device", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),
+    ("tsg_ctx_get_device_input_stats", C.c_int, [_P, C.POINTER(DeviceInputStats)]),
+    ("tsg_test_device_mirror", C.c_int, [_P, _P, C.c_uint64, _U64P, C.c_size_t, _U64P]),
     ("tsg_slot_acquire", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(SlotView)]),
     ("tsg_slot_submit", C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P]),
     ("tsg_slot_release", C.c_int, [_P, C.c_uint32]),

@@ -5,7 +5,8 @@
 // DeviceLane (its own HIP stream and HBM buffers); enqueue_scan puts the whole device part
 // of a batch on that stream with no host round trip:
 //
-//   H2D (pinned slot -> HBM) and one H2D of the file offsets  prep (zero fills, coarse file
+//   H2D (pinned slot -> HBM; for a device-resident batch stage_kernel, caller's HBM -> lane
+//   buffer) and one H2D of the file offsets  prep (zero fills, coarse file
 //   map)  K1  keyword gates  event-chunk compaction  item counts  item layout
 //   (device-side)  item lists  K2  outputs (candidates, keyword bits, overflow / skip
 //   flags, counters: written straight into pinned, host-mapped memory)
@@ -96,6 +97,10 @@ struct ScanInput {
   // and a copy of the offsets behind the batch there, so one H2D carries all three
   uint8_t* room = nullptr;
   uint64_t room_bytes = 0;
+  // a device-resident batch (tsg_device_submit): `total` bytes in the caller's HBM at any
+  // byte alignment, staged into the lane buffer by stage_kernel instead of the content H2D
+  // (data is then null: the pinned slot holds no content until the batch's fetch)
+  const uint8_t* dev_src = nullptr;
 };
 
 // pinned bytes a slot's data buffer keeps past its capacity for that tail and the offsets
@@ -152,5 +157,27 @@ int lane_items(LaneState* l, LaneItems* out);
 // {start, end, group << 32 | items, XCC_ID << 32 | HW_ID}
 int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out);
 int lane_k1f_trace(LaneState* l, std::vector<unsigned long long>* out);  // TSG_K1F_TRACE
+
+// ---- device-resident input: the fetch of the files the host resolver reads
+// A byte range of a batch.  The host lists the ranges of the needed files (adjacent files
+// merged, each range cut to kFetchSegBytes so that one very large file spreads over many
+// blocks) and fetch_kernel copies them from the caller's buffer into the batch's pinned slot
+// at the same offsets.
+struct FetchSeg {
+  uint64_t off, len;
+};
+constexpr uint64_t kFetchSegBytes = 64u << 10;
+// The context's fetch stream (not a lane's: a lane may already run a later batch), its
+// events and the pinned segment list.  Calls are serialized inside.
+struct DeviceFetch;
+int fetch_create(DeviceRules* d, DeviceFetch** out);
+void fetch_destroy(DeviceFetch* f);
+// host_dst[seg) = d_src[seg) for every listed segment of the `total` bytes at d_src;
+// host_dst is pinned, device-visible memory (a slot's data).  Synchronous; *ms = the
+// kernel's HIP-event time.
+int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst,
+                   const FetchSeg* segs, size_t nsegs, float* ms);
+// the whole batch in one runtime D2H (every file is needed)
+int fetch_whole(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, float* ms);
 
 }  // namespace tsg

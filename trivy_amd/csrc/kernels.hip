@@ -260,6 +260,103 @@ __global__ void __launch_bounds__(256) outputs_kernel(OutArgs A) {
   }
 }
 
+// ---------------------------------------------------------------- device-resident input
+// A batch whose bytes the caller already holds in HBM (tsg_device_submit) is staged into the
+// lane buffer by stage_kernel instead of a runtime H2D, and the few files the host resolver
+// will read are copied into the batch's pinned slot by fetch_kernel (the slot is a sparse
+// mirror of the batch: plan.hpp file_needs_scan).  Both are one copy primitive: the
+// destination is written with 16-B vector stores wherever it is 16-B aligned, and the source
+// -- at any offset mod 16: a torch slice -- is read as the two aligned words around each
+// destination word and shifted into place.  No byte before `lo` or at / after `hi` (the
+// caller's buffer) is read: a destination word whose aligned source words would reach
+// outside is put together from byte loads instead; no byte outside [d, d + n) is written:
+// the head up to the destination's alignment and the tail under 16 bytes go bytewise.
+typedef uint32_t c_u32x4 __attribute__((ext_vector_type(4)));
+
+template <bool NT>
+__device__ __forceinline__ void store16(uint8_t* d, c_u32x4 v) {
+  if (NT) __builtin_nontemporal_store(v, (c_u32x4*)d);
+  else *(c_u32x4*)d = v;
+}
+
+// bytes [a, a + 16) of the 32 bytes {w0, w1}, 0 < a < 16 (a is uniform over a copy_span call)
+__device__ __forceinline__ c_u32x4 shift16(c_u32x4 w0, c_u32x4 w1, uint32_t a) {
+  uint32_t v0, v1, v2, v3, v4;
+  switch (a >> 2) {
+    case 0: v0 = w0.x, v1 = w0.y, v2 = w0.z, v3 = w0.w, v4 = w1.x; break;
+    case 1: v0 = w0.y, v1 = w0.z, v2 = w0.w, v3 = w1.x, v4 = w1.y; break;
+    case 2: v0 = w0.z, v1 = w0.w, v2 = w1.x, v3 = w1.y, v4 = w1.z; break;
+    default: v0 = w0.w, v1 = w1.x, v2 = w1.y, v3 = w1.z, v4 = w1.w; break;
+  }
+  const uint32_t r = a & 3u;
+  c_u32x4 o;
+  o.x = __builtin_amdgcn_alignbyte(v1, v0, r);
+  o.y = __builtin_amdgcn_alignbyte(v2, v1, r);
+  o.z = __builtin_amdgcn_alignbyte(v3, v2, r);
+  o.w = __builtin_amdgcn_alignbyte(v4, v3, r);
+  return o;
+}
+
+__device__ __forceinline__ c_u32x4 bytes16(const uint8_t* s) {
+  uint32_t w[4];
+  for (int k = 0; k < 4; k++)
+    w[k] = (uint32_t)s[4 * k] | (uint32_t)s[4 * k + 1] << 8 | (uint32_t)s[4 * k + 2] << 16 | (uint32_t)s[4 * k + 3] << 24;
+  c_u32x4 o;
+  o.x = w[0], o.y = w[1], o.z = w[2], o.w = w[3];
+  return o;
+}
+
+// d[0, n) = s[0, n) by the nth threads of which this is tid; [s, s + n) lies inside [lo, hi)
+template <bool NT>
+__device__ __forceinline__ void copy_span(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, uint64_t n,
+                                          const uint8_t* lo, const uint8_t* hi, uint64_t tid, uint64_t nth) {
+  const uint64_t head = min<uint64_t>(n, (16 - ((uintptr_t)d & 15)) & 15);
+  for (uint64_t i = tid; i < head; i += nth) d[i] = s[i];
+  const uint64_t body = (n - head) / 16;
+  uint8_t* db = d + head;
+  const uint8_t* sb = s + head;
+  const uint32_t a = (uint32_t)((uintptr_t)sb & 15);
+  if (a == 0) {
+    for (uint64_t i = tid; i < body; i += nth) store16<NT>(db + 16 * i, *(const c_u32x4*)(sb + 16 * i));
+  } else {
+    for (uint64_t i = tid; i < body; i += nth) {
+      const uint8_t* p = sb + 16 * i;
+      const uint8_t* w = p - a;  // the aligned word holding p[0]; p[15] lies in the next one
+      c_u32x4 v;
+      if (w >= lo && w + 32 <= hi) v = shift16(*(const c_u32x4*)w, *(const c_u32x4*)(w + 16), a);
+      else v = bytes16(p);
+      store16<NT>(db + 16 * i, v);
+    }
+  }
+  for (uint64_t i = head + body * 16 + tid; i < n; i += nth) d[i] = s[i];
+}
+
+// the caller's batch into the lane buffer (16-B aligned: hipMalloc + kPad), non-temporal
+// stores: the bytes stream through once and K1 reads them next
+__global__ void __launch_bounds__(256) stage_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,
+                                                    uint64_t n) {
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
+  copy_span<true>(dst, src, n, src, src + n, tid, nth);
+}
+
+// segments {offset, length} of the caller's batch into the pinned slot's host-mapped data at
+// the same offsets, a block per segment (the host cuts them to kFetchSegBytes)
+struct FetchArgs {
+  const uint8_t* src;     // the caller's buffer, `total` bytes
+  uint8_t* dst;           // device address of the slot's data
+  const FetchSeg* segs;   // pinned, host-mapped
+  uint32_t nsegs;
+  uint64_t total;
+};
+
+__global__ void __launch_bounds__(256) fetch_kernel(FetchArgs A) {
+  for (uint32_t k = blockIdx.x; k < A.nsegs; k += gridDim.x) {
+    const uint64_t off = A.segs[k].off, len = A.segs[k].len;
+    if (off > A.total || len > A.total - off) continue;  // (never listed: nothing outside the batch is touched)
+    copy_span<false>(A.dst + off, A.src + off, len, A.src, A.src + A.total, threadIdx.x, blockDim.x);
+  }
+}
+
 // ---------------------------------------------------------------- K1
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // 8-byte aligned: one ds_read_b64
@@ -3177,7 +3274,13 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
     const uint64_t at = A.total <= piece * npieces ? k * piece : k * ((A.total - piece) / (npieces - 1));
     if (at >= A.total) break;
     const uint64_t n = std::min<uint64_t>(piece, A.total - at);
-    sample.insert(sample.end(), host_data + at, host_data + at + n);
+    if (host_data) {
+      sample.insert(sample.end(), host_data + at, host_data + at + n);
+    } else {  // device-resident batch: from the staged lane buffer (the stream is idle: synchronized above)
+      const size_t at_s = sample.size();
+      sample.resize(at_s + n);
+      HIP_TRY(hipMemcpy(sample.data() + at_s, A.data + at, n, hipMemcpyDeviceToHost));
+    }
   }
   K1FTables t;
   if (!k1f_build(p, quiet, &t, nullptr, sample.data(), sample.size()))
@@ -3465,7 +3568,16 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     HIP_TRY(hipMemcpyAsync(data, in.room, o_off + meta_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(out->ev[1], st));
   } else {
-    if (total) HIP_TRY(hipMemcpyAsync(data, in.data, total, hipMemcpyHostToDevice, st));
+    if (total && in.dev_src) {
+      // device-resident batch: HBM -> HBM on this lane's stream (one read and one write of the
+      // batch; ev[0]..ev[1], the H2D's place, times it)
+      const uint64_t words = (total + 15) / 16;
+      const int sgrid = (int)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)r->grid));
+      stage_kernel<<<sgrid, 256, 0, st>>>(data, in.dev_src, total);
+      HIP_TRY(hipGetLastError());
+    } else if (total) {
+      HIP_TRY(hipMemcpyAsync(data, in.data, total, hipMemcpyHostToDevice, st));
+    }
     HIP_TRY(hipEventRecord(out->ev[1], st));
     HIP_TRY(hipMemcpyAsync(l->meta, in.off, meta_bytes, hipMemcpyHostToDevice, st));
   }
@@ -3526,7 +3638,8 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     K1FArgs A{data, l->off, l->cf, (uint32_t)total, C, F, k1f_tiles, F ? (uint32_t)ncf : 0u,
               l->kw, l->ev_bits, nullptr, l->counts + kCntK1F, (unsigned long long*)(l->counts + kCntClk),
               nullptr, nullptr, r->k1f_maxlen, 0, nullptr, nullptr};
-    if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.data))) return rc;
+    // (a device-resident batch has no host bytes yet: the sample comes from the staged lane buffer)
+    if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.dev_src ? nullptr : in.data))) return rc;
     if (k1f_list) {
       A.evlist = l->evlist;
       A.nev = l->counts + kCntEvChunks;
@@ -3778,6 +3891,87 @@ int lane_events(LaneState* l, uint32_t* ev, size_t n) {
   HIP_TRY(hipStreamSynchronize(l->st));
   if (n && l->nchunks)
     HIP_TRY(hipMemcpy(ev, l->ev_bits, sizeof(uint32_t) * std::min<uint64_t>(n, l->nchunks), hipMemcpyDeviceToHost));
+  return TSG_OK;
+}
+
+// ---------------------------------------------------------------- device-resident input: fetch
+struct DeviceFetch {
+  DeviceRules* d = nullptr;
+  std::mutex m;  // one fetch at a time (the jobs of two batches may finish together)
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {};
+  FetchSeg* segs = nullptr;  // pinned, host-mapped
+  FetchSeg* segs_dev = nullptr;
+  size_t segs_cap = 0;
+  ~DeviceFetch() {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (st) (void)hipStreamSynchronize(st);
+    if (segs) (void)hipHostFree(segs);
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+int fetch_create(DeviceRules* d, DeviceFetch** out) {
+  HIP_TRY(hipSetDevice(d->device));
+  auto f = std::make_unique<DeviceFetch>();
+  f->d = d;
+  HIP_TRY(hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking));
+  for (auto& e : f->ev) HIP_TRY(hipEventCreate(&e));
+  *out = f.release();
+  return TSG_OK;
+}
+
+void fetch_destroy(DeviceFetch* f) { delete f; }
+
+int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, const FetchSeg* segs,
+                   size_t nsegs, float* ms) {
+  *ms = 0;
+  if (!nsegs) return TSG_OK;
+  if (nsegs > 0xFFFFFFFFu) return fail(TSG_ERR_INTERNAL, "too many fetch segments");
+  for (size_t k = 0; k < nsegs; k++)  // the kernel writes host memory: nothing outside the batch
+    if (segs[k].off > total || segs[k].len > total - segs[k].off)
+      return fail(TSG_ERR_INTERNAL, "fetch segment outside the batch");
+  std::lock_guard<std::mutex> g(f->m);
+  HIP_TRY(hipSetDevice(f->d->device));
+  if (f->segs_cap < nsegs) {
+    if (f->segs) HIP_TRY(hipHostFree(f->segs));
+    f->segs = nullptr;
+    f->segs_cap = 0;
+    const size_t cap = nsegs + nsegs / 2 + 1024;
+    HIP_TRY(hipHostMalloc((void**)&f->segs, sizeof(FetchSeg) * cap, hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&f->segs_dev, f->segs, 0));
+    f->segs_cap = cap;
+  }
+  std::memcpy(f->segs, segs, sizeof(FetchSeg) * nsegs);
+  FetchArgs A{};
+  A.src = d_src;
+  HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
+  A.segs = f->segs_dev;
+  A.nsegs = (uint32_t)nsegs;
+  A.total = total;
+  const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  fetch_kernel<<<grid, 256, 0, f->st>>>(A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  HIP_TRY(hipEventSynchronize(f->ev[1]));  // (a default event: the kernel's host writes are visible)
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  return TSG_OK;
+}
+
+int fetch_whole(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, float* ms) {
+  *ms = 0;
+  if (!total) return TSG_OK;
+  std::lock_guard<std::mutex> g(f->m);
+  HIP_TRY(hipSetDevice(f->d->device));
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  HIP_TRY(hipMemcpyAsync(host_dst, d_src, total, hipMemcpyDeviceToHost, f->st));
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  HIP_TRY(hipEventSynchronize(f->ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
   return TSG_OK;
 }
 

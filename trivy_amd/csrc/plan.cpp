@@ -925,6 +925,15 @@ bool run_segment(const DFA& d, const uint8_t* data, uint64_t fs, uint64_t fe, ui
 
 }  // namespace
 
+std::vector<uint32_t> host_rules(const Plan& plan, const KernelOutputView& ko) {
+  std::vector<uint32_t> out;
+  for (size_t r = 0; r < plan.rule_hostonly.size(); r++)
+    if (plan.rule_hostonly[r] ||
+        (ko.group_skipped && plan.rule_group[r] >= 0 && ko.group_skipped[plan.rule_group[r]]))
+      out.push_back((uint32_t)r);
+  return out;
+}
+
 void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
                    const KernelOutputView& ko, int nthreads, BatchResult* out) {
   const uint32_t F = b.nfiles;
@@ -1006,11 +1015,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
     return x.rule != y.rule ? x.rule < y.rule : x.end < y.end;
   };
 
-  std::vector<uint32_t> hostonly;
-  for (size_t r = 0; r < R; r++)
-    if (plan.rule_hostonly[r] ||
-        (ko.group_skipped && plan.rule_group[r] >= 0 && ko.group_skipped[plan.rule_group[r]]))
-      hostonly.push_back((uint32_t)r);
+  const std::vector<uint32_t> hostonly = host_rules(plan, ko);
   std::vector<uint8_t> kw_has_i(R, 0), kw_has_k(R, 0);
   for (size_t r = 0; r < R; r++)
     for (const auto& k : rs.rules[r].kw_lower) {
@@ -1035,15 +1040,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
   parallel_for(nblk, nthreads, [&](size_t bi) {
     uint32_t cnt = 0;
     for (uint32_t f = (uint32_t)(bi * kBlk), fe = (uint32_t)std::min<size_t>(F, (bi + 1) * kBlk); f < fe; f++) {
-      bool need = first[f] != first[f + 1] || b.offsets[f + 1] == b.offsets[f] ||
-                  (ko.overflow && (ko.overflow[f] & 1)) || !hostonly.empty();
-      if (!need && ko.sparse_kw) {
-        need = (ko.overflow[f] & 2) != 0;
-      } else if (!need) {
-        const uint32_t* kw = ko.kw + (size_t)f * plan.kw_words;
-        for (int k = plan.fb_kw0; k < plan.n_kw && !need; k++) need = (kw[k / 32] >> (k % 32)) & 1;
-      }
-      if (need) {
+      if (file_needs_scan(plan, ko, f, first[f] != first[f + 1], b.offsets[f + 1] == b.offsets[f], !hostonly.empty())) {
         out->slot[f] = 0;
         cnt++;
       } else {

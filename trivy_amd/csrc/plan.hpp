@@ -207,6 +207,27 @@ struct BatchView {
   const uint64_t* path_offsets;  // [nfiles + 1]
 };
 
+// The rules the host resolves alone in this batch: those without a GPU program and those of
+// a group K2 skipped.  While there is one, every file needs the exact scan.
+std::vector<uint32_t> host_rules(const Plan& plan, const KernelOutputView& ko);
+
+// Does the host resolver read file f's bytes (resolve_batch), or is the file settled by
+// Global.AllowPath alone?  It reads a file with a candidate record, an empty file, a file
+// whose overflow flag (bit 0) is set, a file with folding-rune keyword bits, and every file
+// while a host rule exists (any_host: !host_rules().empty()).  The one predicate of the
+// resolver and of the fetch of a device-resident batch (pipeline.cpp), whose pinned mirror
+// holds only the files this names: has_cand is "a candidate of f after the expansion of word
+// records" in the resolver and "a record of f" in the fetch, which includes it.
+inline bool file_needs_scan(const Plan& plan, const KernelOutputView& ko, uint32_t f, bool has_cand, bool empty,
+                            bool any_host) {
+  if (has_cand || empty || (ko.overflow && (ko.overflow[f] & 1)) || any_host) return true;
+  if (ko.sparse_kw) return (ko.overflow[f] & 2) != 0;
+  const uint32_t* kw = ko.kw + (size_t)f * plan.kw_words;
+  for (int k = plan.fb_kw0; k < plan.n_kw; k++)
+    if ((kw[k / 32] >> (k % 32)) & 1) return true;
+  return false;
+}
+
 // Start offsets of the folding runes in s: which = 1 U+0130, 2 U+212A, 4 U+017F (ORed).
 void fold_rune_positions(const uint8_t* s, int64_t n, uint32_t which, std::vector<int64_t>* out);
 

@@ -490,6 +490,9 @@ class GpuContext:
         self._lock = threading.Lock()
         self._fifo = []         # (ticket, paths) of this object's uncollected submissions
         self._paths = {}        # ticket -> paths
+        self._tensors = {}      # ticket -> the tensor of a submit_tensor, alive until collect
+        self._device = int(device)
+        self._emulate = bool(emulate)
 
     @classmethod
     def borrowed(cls, scanner, handle, chunk_bytes=0):
@@ -506,6 +509,9 @@ class GpuContext:
         self._lock = threading.Lock()
         self._fifo = []
         self._paths = {}
+        self._tensors = {}
+        self._device = None     # (the owner knows; submit_tensor then only asks for a GPU tensor)
+        self._emulate = False
         return self
 
     @property
@@ -618,13 +624,19 @@ class GpuContext:
         handle; the caller frees it."""
         ticket, _ = self._take(ticket)
         out = C.c_void_p()
-        N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
+        try:
+            N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
+        finally:
+            self._tensors.pop(ticket, None)
         return out
 
     def collect(self, ticket=None):
         ticket, paths = self._take(ticket)
         out = C.c_void_p()
-        N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
+        try:
+            N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
+        finally:
+            self._tensors.pop(ticket, None)  # (a submit_tensor's tensor: the batch is done)
         return self.scanner.decode(out, self._paths_of(paths))
 
     def pending(self):
@@ -641,10 +653,88 @@ class GpuContext:
         N.check(N.lib().tsg_scan_batch(self._h, *batch.ptrs(), C.byref(out)))
         return self.scanner.decode(out, self._paths_of(batch))
 
+    def _tensor_args(self, data, offsets, paths):
+        """Checked arguments of tsg_device_submit for a tensor: raises before any native
+        call.  Returns (pointer, offsets, nfiles, path bytes, path offsets, paths)."""
+        import torch
+        if not isinstance(data, torch.Tensor):
+            raise TypeError("data must be a torch.Tensor, not %s" % type(data).__name__)
+        if data.dtype != torch.uint8:
+            raise TypeError("data must be a torch.uint8 tensor, not %s" % data.dtype)
+        if data.dim() != 1 or not data.is_contiguous():
+            raise ValueError("data must be 1-D and contiguous")
+        if self._emulate:
+            if data.device.type != "cpu":
+                raise ValueError("an emulated context scans host tensors, not %s" % data.device)
+        elif data.device.type != "cuda" or (self._device is not None and data.device.index != self._device):
+            raise ValueError("data is on %s, the context on device %s" % (data.device, self._device))
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.ndim != 1 or len(offs) < 1 or int(offs[0]) != 0:
+            raise ValueError("offsets must be 1-D and start at 0")
+        if (offs[1:] < offs[:-1]).any():
+            raise ValueError("offsets must be non-decreasing")
+        if int(offs[-1]) > data.numel():
+            raise ValueError("offsets cover %d bytes, the tensor holds %d" % (int(offs[-1]), data.numel()))
+        paths = list(paths)
+        if len(paths) != len(offs) - 1:
+            raise ValueError("%d paths for %d files" % (len(paths), len(offs) - 1))
+        pb = [_b(p) for p in paths]
+        poffs = np.zeros(len(pb) + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(p) for p in pb], dtype=np.uint64), out=poffs[1:])
+        blob = np.frombuffer(b"".join(pb) or b"\0", dtype=np.uint8)
+        if data.device.type == "cuda":
+            # the bytes must be written when the library's own streams read them
+            torch.cuda.current_stream(data.device).synchronize()
+        u64p = C.POINTER(C.c_uint64)
+        return (C.c_void_p(data.data_ptr() if data.numel() else None), offs.ctypes.data_as(u64p),
+                C.c_uint32(len(pb)), C.c_void_p(blob.ctypes.data), poffs.ctypes.data_as(u64p)), (offs, blob, poffs), paths
+
+    def submit_tensor(self, data, offsets, paths):
+        """tsg_device_submit: scan files that already live in this device's memory.  data is a
+        1-D contiguous torch.uint8 tensor on the context's device (a slice with a storage
+        offset is fine: any byte alignment), file i = data[offsets[i]:offsets[i + 1]], paths
+        the files' names.  The current torch stream is synchronized first; the tensor is kept
+        alive, and must stay unchanged, until collect(ticket).  Returns the ticket."""
+        args, keep, paths = self._tensor_args(data, offsets, paths)
+        t = C.c_uint64()
+        N.check(N.lib().tsg_device_submit(self._h, *args, C.byref(t)))
+        del keep  # (host arrays: copied by the call)
+        with self._lock:
+            self._tensors[t.value] = data
+        return self._track(t.value, paths)
+
+    def scan_tensor(self, data, offsets, paths):
+        """tsg_scan_device: submit_tensor + collect in one thread-safe call; the findings are
+        scan_batch's for the same bytes."""
+        args, keep, paths = self._tensor_args(data, offsets, paths)
+        out = C.c_void_p()
+        N.check(N.lib().tsg_scan_device(self._h, *args, C.byref(out)))
+        del keep
+        return self.scanner.decode(out, paths)
+
     def stats(self):
         s = N.Stats()
         N.check(N.lib().tsg_ctx_get_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in N.Stats._fields_}
+
+    def device_input_stats(self):
+        """tsg_device_input_stats of the context's device-resident batches."""
+        s = N.DeviceInputStats()
+        N.check(N.lib().tsg_ctx_get_device_input_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in N.DeviceInputStats._fields_}
+
+    def device_mirror(self):
+        """Test hook (tsg_test_device_mirror): the pinned mirror of the last finished
+        device-resident batch as (bytes [total], segments [n, 2] of (offset, length))."""
+        n = (C.c_uint64 * 2)()
+        N.check(N.lib().tsg_test_device_mirror(self._h, None, 0, None, 0, n))
+        data = np.zeros(max(int(n[0]), 1), dtype=np.uint8)
+        segs = np.zeros((max(int(n[1]), 1), 2), dtype=np.uint64)
+        m = (C.c_uint64 * 2)()
+        N.check(N.lib().tsg_test_device_mirror(self._h, C.c_void_p(data.ctypes.data), int(n[0]),
+                                               segs.ctypes.data_as(C.POINTER(C.c_uint64)), int(n[1]), m))
+        assert list(m) == list(n)
+        return data[:int(n[0])], segs[:int(n[1])]
 
     def close(self):
         if self._h:
@@ -652,7 +742,8 @@ class GpuContext:
                 N.lib().tsg_slot_release(self._h, self._upload[0])
                 self._upload = None
             if self._owned:
-                N.lib().tsg_ctx_destroy(self._h)
+                N.lib().tsg_ctx_destroy(self._h)  # (waits for the batches in flight)
+                self._tensors.clear()
             self._h = None
 
     def __del__(self):
