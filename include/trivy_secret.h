@@ -16,6 +16,10 @@
  *       scanner.go:341-416                            tsg_scan_batch (many files, GPU)
  *                                                     tsg_scan_device (many files already
  *                                                       in this GPU's memory)
+ *                                                     tsg_scan_device_spans (the same, as
+ *                                                       spans of one device buffer)
+ *   utils.IsBinary in SecretAnalyzer.Analyze          TSG_SPANS_BINARY_GATE (on the device)
+ *       secret.go:78-84, utils.go:71-89
  *   SecretAnalyzer.Analyze per-file goroutines        tsg_queue_scan (concurrent callers
  *       analyzer/secret/secret.go:78-110,               coalesced into pinned batches),
  *       analyzer.go:419-443                             tsg_slot_* / tsg_scan_batch (batches)
@@ -28,7 +32,8 @@
  * caller's own slot and submission ticket; none acts on "the last" batch); a tsg_ruleset
  * is immutable and may be shared by any number of threads and contexts.  The library never
  * retains a caller pointer past a call, with one documented exception: the device buffer of
- * tsg_device_submit, which the caller leaves untouched until the ticket is collected.
+ * tsg_device_submit / tsg_device_spans_submit, which the caller leaves untouched until the
+ * ticket is collected.
  *
  * Result format (tsg_result_data), little endian:
  *   u32 magic 'TSG1' (0x31475354), u32 nfiles, then per file:
@@ -334,6 +339,53 @@ int tsg_ctx_get_device_input_stats(const tsg_ctx* ctx, tsg_device_input_stats* o
 int tsg_test_device_mirror(tsg_ctx* ctx, uint8_t* data, uint64_t data_cap, uint64_t* segs,
                            size_t segs_cap, uint64_t* n);
 
+/* -- Device-resident input, files as spans of one device buffer ------------------------
+ * What a GPU decompressor leaves behind is a layer tar: file bodies at arbitrary offsets,
+ * headers between them, binaries among them.  File i is the lengths[i] bytes at offset
+ * starts[i] of the base_bytes bytes at d_base (a device pointer on the context's device, any
+ * alignment; base_bytes may be far more than one batch holds: only the listed spans count).
+ * Spans may come in any order, with gaps, and may overlap.  With TSG_SPANS_BINARY_GATE a
+ * kernel applies utils.IsBinary (utils.go:71-89: a control byte in the first
+ * min(length, 300) bytes) to every span and the binary files are dropped as
+ * SecretAnalyzer.Analyze drops them (secret.go:78-84); the submitting thread waits for that
+ * kernel (the only wait of the call), so kept[i] (1 = scanned, 0 = dropped; may be NULL) is
+ * final when the call returns.  A kernel then gathers the kept spans back to back, in input
+ * order, into the lane's buffer in the staging copy's place, every scan kernel runs
+ * unchanged, and afterwards only the files the host resolver reads are gathered into the
+ * batch's pinned slot (never the whole buffer).  The result holds one record per KEPT file,
+ * in input order; no kept file is a valid, empty result.  The sum of the lengths obeys the
+ * limits of tsg_device_submit's batch, and the slot is as large as that sum.  The caller
+ * leaves the buffer untouched until the ticket is collected.  Results are byte-identical to
+ * tsg_scan_batch's for the kept files' bytes.  TSG_ERR_ARG: NULL context or out pointer, a
+ * span that is not inside [0, base_bytes) (start + length overflowing included), NULL d_base
+ * with a non-empty span, unknown flag bits; the context keeps working after it.  Under
+ * TSG_CTX_EMULATE d_base is a host pointer, the gate runs on the CPU and the gathers are
+ * memcpy of the same segment lists.  These batches count in tsg_device_input_stats too
+ * (stage_ms = the gather, whole_batch_copy = 0), the device_poison knob applies, and
+ * tsg_test_device_mirror shows their mirror and segments in the kept files' back-to-back
+ * coordinates. */
+#define TSG_SPANS_BINARY_GATE 1u   /* drop files utils.IsBinary calls binary (device-side) */
+int tsg_device_spans_submit(tsg_ctx* ctx, const void* d_base, uint64_t base_bytes,
+                            const uint64_t* starts, const uint64_t* lengths, uint32_t nfiles,
+                            const char* paths, const uint64_t* path_offsets, uint32_t flags,
+                            uint8_t* kept, uint64_t* ticket);
+int tsg_scan_device_spans(tsg_ctx* ctx, const void* d_base, uint64_t base_bytes,
+                          const uint64_t* starts, const uint64_t* lengths, uint32_t nfiles,
+                          const char* paths, const uint64_t* path_offsets, uint32_t flags,
+                          uint8_t* kept, tsg_result** out);
+typedef struct tsg_device_spans_stats {
+  /* last finished spans batch */
+  double gate_ms;        /* binary_gate_kernel by HIP events (wall time when emulated); 0 = gate off */
+  double gather_ms;      /* the staging gather by HIP events (= tsg_device_input_stats.stage_ms); 0 emulated */
+  double wait_ms;        /* wall time the submitting thread waited for the gate */
+  uint64_t files_in, files_kept, files_dropped;
+  uint64_t bytes_in, bytes_kept; /* sum of all lengths, of the kept files' lengths */
+  /* all spans batches so far */
+  uint64_t batches, sum_files_in, sum_files_kept, sum_files_dropped, sum_bytes_in, sum_bytes_kept;
+  double sum_gate_ms, sum_gather_ms, sum_wait_ms;
+} tsg_device_spans_stats;
+int tsg_ctx_get_device_spans_stats(const tsg_ctx* ctx, tsg_device_spans_stats* out);
+
 /* -- Submission queue for concurrent per-file callers ----------------------------------
  * The analyzer framework calls Analyze -> Scan from one goroutine per file
  * (pkg/fanal/analyzer/analyzer.go:419-443).  tsg_queue_scan is that Scan: any number of
@@ -405,7 +457,7 @@ const char* tsg_last_error(void);
  *   "k2_no_word_recs" "1": K2 writes a record per accepting transition instead of one per
  *                     accepting 16-B word, as for rule sets of 16,384 groups and more (the
  *                     emulation then ignores emu_wordrec)
- *   "device_poison"   "1": tsg_device_submit fills the batch's pinned mirror, before the
+ *   "device_poison"   "1": tsg_device_submit / tsg_device_spans_submit fill the batch's pinned mirror, before the
  *                     fetch, with a repeating line that the builtin rules match (an AWS access
  *                     key id): a resolver read of a byte that was not fetched shows up as a
  *                     wrong finding

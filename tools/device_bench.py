@@ -2,6 +2,7 @@
 """Device-resident input against the PCIe path, same bytes, same context.
 
     python tools/device_bench.py [--gb 4] [--steps 20] [--rounds 3] [--warmup 1] [--depth 4]
+    python tools/device_bench.py --spans [--gb 1] [--batch-mib 256] ...
 
 The configs[1] workload of bench.py (builtin rules over the seeded corpus, seed 2, in
 batches of --batch-mib) is scanned two ways on one GpuContext:
@@ -18,7 +19,23 @@ resident path, and the share of the bytes that was fetched.  The two paths are t
 alternation, --rounds windows of --steps passes each after --warmup passes, with the host
 clock over whole windows (every result collected); the line carries every window's GB/s
 and the medians.  The per-stage figures are the library's HIP-event times of the last
-window (tsg_stats, tsg_device_input_stats)."""
+window (tsg_stats, tsg_device_input_stats).
+
+--spans measures tsg_device_spans_submit instead (GpuContext.scan_spans' entry point).  The
+seeded corpus is laid out as a decompressed layer would be: the files in order with 512
+bytes between them, 30 % of them binary blobs (random bytes from the first byte on, which
+utils.IsBinary drops), uploaded once as one tensor.  Two paths run in alternation on one
+context, over the same kept bytes:
+
+  spans     the files as (start, length) spans of that tensor, the binary gate on: gate
+            kernel, the submit-side wait for it, the gather into the lane buffer
+  compact   the parent path: the kept files packed back to back on the host beforehand
+            (the pre-compaction is not timed), uploaded once, tsg_device_submit
+
+Every batch's result bytes of the two paths are compared, and the kept mask is compared
+with IsBinary on the host.  The JSON line carries GB/s of kept bytes of both paths per
+window, and per batch the gate, the submit wait and the gather beside the compact path's
+stage_ms, each as the mean of every window (so the spread between windows shows)."""
 import argparse
 import collections
 import ctypes as C
@@ -44,7 +61,12 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--emulate", action="store_true",
                     help="dry run of this script without a GPU (emulated context, host tensors)")
+    ap.add_argument("--spans", action="store_true",
+                    help="files as spans of one buffer with 30 %% binary blobs against scan_tensor "
+                         "over the pre-compacted kept bytes")
     args = ap.parse_args()
+    if args.spans:
+        return main_spans(args)
 
     import numpy as np
     import torch
@@ -167,6 +189,162 @@ def main():
     ctx.close()
     print(json.dumps(line))
     return 0 if equal else 1
+
+
+def main_spans(args):
+    import numpy as np
+    import torch
+    from trivy_amd import _native as N
+    from trivy_amd import corpus
+    from trivy_amd import secret as S
+
+    def log(msg):
+        print(msg, file=sys.stderr, flush=True)
+
+    GAP = 512
+    L = N.lib()
+    sc = S.NewScanner(None)
+    t0 = time.perf_counter()
+    batch, info = corpus.make_corpus(int(args.gb * (1 << 30)), seed=args.seed, plants_per_mib=1.0)
+    offs = batch.offsets.astype(np.int64)
+    sizes = np.diff(offs)
+    F = len(sizes)
+    rng = np.random.default_rng(args.seed + 1000)
+    blob = rng.random(F) < 0.3
+    starts = np.cumsum(sizes + GAP) - sizes  # 512 bytes before every file
+    buf = np.zeros(int(starts[-1] + sizes[-1]) + GAP, dtype=np.uint8)
+    for f in range(F):
+        a, n = int(starts[f]), int(sizes[f])
+        if blob[f]:
+            buf[a:a + n] = rng.integers(0, 256, size=n, dtype=np.uint8)
+        else:
+            buf[a:a + n] = batch.data[offs[f]:offs[f] + n]
+    # utils.IsBinary on the host: the reference of the kept mask
+    ctl = np.zeros(256, dtype=bool)
+    for b in range(256):
+        ctl[b] = b < 7 or b == 11 or 13 < b < 27 or 27 < b < 0x20 or b == 0x7F
+    binary = np.array([ctl[buf[int(starts[f]):int(starts[f]) + min(int(sizes[f]), 300)]].any() for f in range(F)])
+    keep = ~binary
+    log("corpus %.2f GiB, %d files (%d binary), laid out in %.2f GiB, in %.1fs" % (
+        sizes.sum() / (1 << 30), F, int(binary.sum()), len(buf) / (1 << 30), time.perf_counter() - t0))
+    dev = "cpu" if args.emulate else "cuda:%d" % args.device
+    whole = torch.from_numpy(buf).to(dev)
+    # batches: runs of files holding about --batch-mib of kept bytes
+    cuts, acc = [0], 0
+    for f in range(F):
+        acc += int(sizes[f]) if keep[f] else 0
+        if acc >= (args.batch_mib << 20):
+            cuts.append(f + 1)
+            acc = 0
+    if cuts[-1] != F:
+        cuts.append(F)
+    ctx = S.GpuContext(sc, args.device, max_slots=2 * args.depth + 4, emulate=args.emulate)
+    paths = [batch.path(i) for i in range(F)]
+    span_args, compact_args, tensors, kept_bytes = [], [], [], 0
+    for a, e in zip(cuts[:-1], cuts[1:]):
+        k = np.flatnonzero(keep[a:e]) + a
+        span_args.append(ctx._spans_args(whole, starts[a:e], sizes[a:e], paths[a:e], True))
+        packed = np.concatenate([buf[int(starts[f]):int(starts[f] + sizes[f])] for f in k] or [np.zeros(0, np.uint8)])
+        o = np.zeros(len(k) + 1, dtype=np.uint64)
+        np.cumsum(sizes[k], out=o[1:])
+        t = torch.from_numpy(packed).to(dev)
+        tensors.append(t)
+        compact_args.append(ctx._tensor_args(t, o, [paths[f] for f in k]))
+        kept_bytes += int(sizes[k].sum())
+    if not args.emulate:
+        torch.cuda.synchronize()
+    nb = len(span_args)
+    log("%d batches, %.3f GiB kept of %.3f GiB listed" % (nb, kept_bytes / (1 << 30), sizes.sum() / (1 << 30)))
+
+    def raw(out):
+        n = C.c_size_t()
+        p = L.tsg_result_data(out, C.byref(n))
+        data = C.string_at(p, n.value)
+        L.tsg_result_free(out)
+        return data
+
+    def submit_spans(i):
+        tk = C.c_uint64()
+        N.check(L.tsg_device_spans_submit(ctx.handle, *span_args[i][0], C.byref(tk)))
+        return tk.value
+
+    def submit_compact(i):
+        tk = C.c_uint64()
+        N.check(L.tsg_device_submit(ctx.handle, *compact_args[i][0], C.byref(tk)))
+        return tk.value
+
+    def run(submit, steps, keep_last):
+        q, got = collections.deque(), {}
+
+        def collect():
+            t, k, i = q.popleft()
+            out = C.c_void_p()
+            N.check(L.tsg_batch_collect(ctx.handle, t, C.byref(out)))
+            if keep_last and k == steps - 1:
+                got[i] = raw(out)
+            else:
+                L.tsg_result_free(out)
+        for k in range(steps):
+            for i in range(nb):
+                q.append((submit(i), k, i))
+                while len(q) >= args.depth:
+                    collect()
+        while q:
+            collect()
+        return got
+
+    def sums(d):
+        return {k: v for k, v in d.items() if k.startswith("sum_") or k == "batches"}
+
+    def timed(submit):
+        run(submit, args.warmup, False)
+        s0, d0, p0 = sums(ctx.stats()), sums(ctx.device_input_stats()), sums(ctx.device_spans_stats())
+        t0 = time.perf_counter()
+        got = run(submit, args.steps, True)
+        dt = time.perf_counter() - t0
+        s1, d1, p1 = sums(ctx.stats()), sums(ctx.device_input_stats()), sums(ctx.device_spans_stats())
+        return got, dt, {k: s1[k] - s0[k] for k in s1}, {k: d1[k] - d0[k] for k in d1}, {k: p1[k] - p0[k] for k in p1}
+
+    sg, cg, equal, kept_equal = [], [], True, True
+    win = {"gate": [], "wait": [], "gather": [], "stage": [], "spans_fetch": [], "compact_fetch": [], "spans_k1": [],
+           "compact_k1": []}
+    for _ in range(max(1, args.rounds)):
+        sk, sdt, ss, sd, sp = timed(submit_spans)
+        for (a, e), sa in zip(zip(cuts[:-1], cuts[1:]), span_args):
+            kept_equal = kept_equal and bool((sa[3].astype(bool) == keep[a:e]).all())
+        ck, cdt, cs, cd, _ = timed(submit_compact)
+        equal = equal and all(sk[i] == ck[i] for i in range(nb))
+        sg.append(round(kept_bytes * args.steps / sdt / 1e9, 3))
+        cg.append(round(kept_bytes * args.steps / cdt / 1e9, 3))
+        n = max(1, sp["batches"])
+        m = max(1, cd["batches"])
+        win["gate"].append(round(sp["sum_gate_ms"] / n, 4))
+        win["wait"].append(round(sp["sum_wait_ms"] / n, 4))
+        win["gather"].append(round(sp["sum_gather_ms"] / n, 4))
+        win["stage"].append(round(cd["sum_stage_ms"] / m, 4))
+        win["spans_fetch"].append(round(sd["sum_fetch_ms"] / n, 4))
+        win["compact_fetch"].append(round(cd["sum_fetch_ms"] / m, 4))
+        win["spans_k1"].append(round(ss["sum_k1_ms"] / n, 4))
+        win["compact_k1"].append(round(cs["sum_k1_ms"] / m, 4))
+    st = ctx.device_spans_stats()
+    line = {
+        "metric": "secret-scan GB/s of kept bytes (builtin rules), spans of a device buffer with the binary gate "
+                  "vs scan_tensor over pre-compacted bytes, 1 MI355X",
+        "spans_gbs": round(float(np.median(sg)), 3), "compact_gbs": round(float(np.median(cg)), 3), "unit": "GB/s",
+        "spans_gbs_windows": sg, "compact_gbs_windows": cg,
+        "findings_equal": equal, "kept_equals_isbinary": kept_equal,
+        "files": F, "files_kept": int(keep.sum()), "files_dropped": int(binary.sum()),
+        "listed_gib": round(float(sizes.sum()) / (1 << 30), 3), "kept_gib": round(kept_bytes / (1 << 30), 3),
+        "buffer_gib": round(len(buf) / (1 << 30), 3), "gap_bytes": GAP,
+        "batches": nb, "batch_mib": args.batch_mib, "steps": args.steps, "rounds": args.rounds,
+        "warmup": args.warmup, "depth": args.depth,
+        "per_batch_ms_windows": win,
+        "per_batch_ms": {k: round(float(np.median(v)), 4) for k, v in win.items()},
+        "last_batch": {k: st[k] for k in ("files_in", "files_kept", "files_dropped", "bytes_in", "bytes_kept")},
+    }
+    ctx.close()
+    print(json.dumps(line))
+    return 0 if equal and kept_equal else 1
 
 
 if __name__ == "__main__":

@@ -100,6 +100,19 @@ class DeviceInputStats(C.Structure):
                 ("sum_fetch_ms", C.c_double), ("whole_batch_copy", C.c_uint32)]
 
 
+class DeviceSpansStats(C.Structure):
+    """tsg_device_spans_stats, in the header's order."""
+    _fields_ = [("gate_ms", C.c_double), ("gather_ms", C.c_double), ("wait_ms", C.c_double),
+                ("files_in", C.c_uint64), ("files_kept", C.c_uint64), ("files_dropped", C.c_uint64),
+                ("bytes_in", C.c_uint64), ("bytes_kept", C.c_uint64),
+                ("batches", C.c_uint64), ("sum_files_in", C.c_uint64), ("sum_files_kept", C.c_uint64),
+                ("sum_files_dropped", C.c_uint64), ("sum_bytes_in", C.c_uint64),
+                ("sum_bytes_kept", C.c_uint64), ("sum_gate_ms", C.c_double),
+                ("sum_gather_ms", C.c_double), ("sum_wait_ms", C.c_double)]
+
+
+TSG_SPANS_BINARY_GATE = 1
+
 # (name, restype, argtypes) -- every symbol include/trivy_secret.h declares
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
@@ -134,6 +147,11 @@ SIGNATURES = [
     ("tsg_scan_device", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),
     ("tsg_ctx_get_device_input_stats", C.c_int, [_P, C.POINTER(DeviceInputStats)]),
     ("tsg_test_device_mirror", C.c_int, [_P, _P, C.c_uint64, _U64P, C.c_size_t, _U64P]),
+    ("tsg_device_spans_submit", C.c_int, [_P, _P, C.c_uint64, _U64P, _U64P, C.c_uint32, _P, _U64P, C.c_uint32,
+                                          _U8P, _U64P]),
+    ("tsg_scan_device_spans", C.c_int, [_P, _P, C.c_uint64, _U64P, _U64P, C.c_uint32, _P, _U64P, C.c_uint32,
+                                        _U8P, C.POINTER(_P)]),
+    ("tsg_ctx_get_device_spans_stats", C.c_int, [_P, C.POINTER(DeviceSpansStats)]),
     ("tsg_slot_acquire", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(SlotView)]),
     ("tsg_slot_submit", C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P]),
     ("tsg_slot_release", C.c_int, [_P, C.c_uint32]),

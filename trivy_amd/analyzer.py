@@ -105,6 +105,25 @@ class SecretAnalyzer:
         secrets = [r for r in res if r["Findings"]]
         return sort_secrets(secrets)
 
+    def AnalyzeTensor(self, data, starts, lengths, file_paths, dir="", ctx=None):
+        """AnalyzeBatch for files whose bytes already lie in GPU memory: file i is
+        data[starts[i]:starts[i] + lengths[i]] of a torch.uint8 tensor on ctx's device (a
+        decompressed layer tar, say) and file_paths[i] its name.  `Required(path, size)` and
+        the "/" prefix of an empty `dir` are settled here on the host; the binary gate
+        (secret.go:78-84) runs on the device, and only the files the resolver reads come
+        back (GpuContext.scan_spans).  Returns the merged, sorted AnalysisResult.Secrets."""
+        import numpy as np
+        if ctx is None:
+            raise ValueError("AnalyzeTensor needs a GpuContext (ctx=...)")
+        file_paths = list(file_paths)
+        starts, lengths = np.asarray(starts), np.asarray(lengths)
+        if not (len(starts) == len(lengths) == len(file_paths)):
+            raise ValueError("%d starts, %d lengths, %d paths" % (len(starts), len(lengths), len(file_paths)))
+        idx = [i for i, p in enumerate(file_paths) if self.Required(p, int(lengths[i]))]
+        paths = [self._scan_path(AnalysisInput(dir, file_paths[i], b"")) for i in idx]
+        res, _ = ctx.scan_spans(data, starts[idx], lengths[idx], paths, binary_gate=True)
+        return sort_secrets([r for r in res if r["Findings"]])
+
 
 def _go_sort(items, key, secondary=None):
     """sort.Slice (Go 1.19 pdqsort_func, unstable) of `items` in place by (key bytes,

@@ -6,7 +6,7 @@
 // of a batch on that stream with no host round trip:
 //
 //   H2D (pinned slot -> HBM; for a device-resident batch stage_kernel, caller's HBM -> lane
-//   buffer) and one H2D of the file offsets  prep (zero fills, coarse file
+//   buffer, or gather_kernel for files given as spans of the caller's buffer) and one H2D of the file offsets  prep (zero fills, coarse file
 //   map)  K1  keyword gates  event-chunk compaction  item counts  item layout
 //   (device-side)  item lists  K2  outputs (candidates, keyword bits, overflow / skip
 //   flags, counters: written straight into pinned, host-mapped memory)
@@ -86,6 +86,13 @@ struct K2Diag {
   unsigned long long tail_bytes, tail_max, long_tails, replays;
 };
 
+// A segment of a gather (gather_kernel): `len` bytes at offset `src` of the caller's buffer
+// go to offset `dst` of the destination.  The host lists them (files merged only where they
+// are adjacent in both buffers, each cut to kFetchSegBytes).
+struct GatherSeg {
+  uint64_t src, dst, len;
+};
+
 struct ScanInput {
   const uint8_t* data;       // pinned host, `total` bytes
   const uint64_t* off;       // [nfiles + 1]
@@ -101,6 +108,14 @@ struct ScanInput {
   // byte alignment, staged into the lane buffer by stage_kernel instead of the content H2D
   // (data is then null: the pinned slot holds no content until the batch's fetch)
   const uint8_t* dev_src = nullptr;
+  // spans of a device buffer (tsg_device_spans_submit): dev_src is the caller's buffer of
+  // src_bytes bytes and gather_kernel copies these segments of it into the lane buffer in
+  // the stage's place.  `gather` is non-null for every such batch (ngather may be 0) and
+  // lies in pinned memory that outlives the batch's kernels; gather_dev is its device address.
+  const GatherSeg* gather = nullptr;
+  const GatherSeg* gather_dev = nullptr;
+  uint32_t ngather = 0;
+  uint64_t src_bytes = 0;
 };
 
 // pinned bytes a slot's data buffer keeps past its capacity for that tail and the offsets
@@ -177,6 +192,16 @@ void fetch_destroy(DeviceFetch* f);
 // kernel's HIP-event time.
 int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst,
                    const FetchSeg* segs, size_t nsegs, float* ms);
+// Spans of a device buffer: flags[f] = utils.IsBinary of the span {starts[f], lengths[f]} of
+// the base_bytes bytes at d_base (binary_gate_kernel on the fetch stream).  The three arrays
+// are device addresses of pinned, host-mapped memory; the host has checked every span
+// against the buffer.  Synchronous: the flags are readable on return; *ms = HIP-event time.
+int gate_spans(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, const uint64_t* starts_dev,
+               const uint64_t* lengths_dev, uint8_t* flags_dev, uint32_t nfiles, float* ms);
+// host_dst[seg.dst, +len) = d_base[seg.src, +len) for every listed segment (gather_kernel);
+// host_dst is pinned, device-visible memory of dst_bytes bytes.  Synchronous, as fetch_segments.
+int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uint8_t* host_dst, uint64_t dst_bytes,
+                 const GatherSeg* segs, size_t nsegs, float* ms);
 // the whole batch in one runtime D2H (every file is needed)
 int fetch_whole(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, float* ms);
 

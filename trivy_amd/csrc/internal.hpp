@@ -27,6 +27,8 @@ int fail(int code, const std::string& msg);
 const tsg_ruleset* ctx_ruleset(const tsg_ctx* c);
 // bytes of a default pinned slot (tsg_ctx_options.slot_mib)
 uint64_t ctx_slot_bytes(const tsg_ctx* c);
+// utils.IsBinary (utils.go:71-89) of a file of n bytes at p: layer.cpp's is_binary
+bool is_binary_head(const uint8_t* p, uint64_t n);
 
 // test and measurement knobs (knobs.cpp, tsg_test_knob); 0 = default
 struct Knobs {

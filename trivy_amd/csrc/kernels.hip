@@ -357,6 +357,65 @@ __global__ void __launch_bounds__(256) fetch_kernel(FetchArgs A) {
   }
 }
 
+// Files given as spans of a device buffer (tsg_device_spans_submit): a layer tar in HBM, its
+// file bodies at any offsets, in any order, with gaps.  binary_gate_kernel is utils.IsBinary
+// (utils.go:71-89) per span, a wave per file: lane l looks at bytes l, l + 64, ... of the
+// first min(length, 300), bytewise (any alignment; nothing outside the span is read, so
+// nothing outside the buffer), and one ballot folds the wave's verdict, which lane 0 stores
+// as the file's flag byte in pinned, host-mapped memory.
+struct SpanGateArgs {
+  const uint8_t* base;      // the caller's buffer, `base_bytes` bytes
+  uint64_t base_bytes;
+  const uint64_t* starts;   // [nfiles] pinned, host-mapped
+  const uint64_t* lengths;  // [nfiles]
+  uint8_t* flags;           // [nfiles] out, pinned, host-mapped: 1 = binary
+  uint32_t nfiles;
+};
+constexpr uint32_t kGateHead = 300;  // utils.go:74-77
+
+__global__ void __launch_bounds__(256) binary_gate_kernel(SpanGateArgs A) {
+  const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64;
+  for (uint64_t f = (uint64_t)blockIdx.x * wpb + threadIdx.x / 64; f < A.nfiles; f += (uint64_t)gridDim.x * wpb) {
+    const uint64_t start = A.starts[f], len = A.lengths[f];  // (uniform over the wave)
+    bool bad = false;
+    if (start <= A.base_bytes && len <= A.base_bytes - start) {  // (never listed otherwise)
+      const uint32_t h = (uint32_t)min<uint64_t>(len, kGateHead);
+      const uint8_t* p = A.base + start;
+      for (uint32_t i = lane; i < h; i += 64) {
+        const uint32_t b = p[i];
+        bad |= b < 7 || b == 11 || (13 < b && b < 27) || (27 < b && b < 0x20) || b == 0x7f;
+      }
+    }
+    const unsigned long long m = __ballot(bad);
+    if (lane == 0) A.flags[f] = m != 0 ? 1 : 0;
+  }
+}
+
+// gather_kernel copies segments {src, dst, len} of the caller's buffer to dst + seg.dst, a
+// block per segment (the host cuts them to kFetchSegBytes; source and destination alignment
+// differ per segment, copy_span's shift is uniform per call).  NT: into the lane buffer in
+// stage_kernel's place, the kept files back to back; !NT: the files the resolver reads into
+// the pinned mirror at their compacted offsets.  A segment that leaves either buffer is
+// skipped (the host lists none); copy_span writes nothing outside [dst, dst + len), so two
+// blocks' adjacent segments never share a byte.
+struct GatherArgs {
+  const uint8_t* src;      // the caller's buffer, `src_bytes` bytes
+  uint64_t src_bytes;
+  uint8_t* dst;
+  uint64_t dst_bytes;
+  const GatherSeg* segs;   // pinned, host-mapped
+  uint32_t nsegs;
+};
+
+template <bool NT>
+__global__ void __launch_bounds__(256) gather_kernel(GatherArgs A) {
+  for (uint32_t k = blockIdx.x; k < A.nsegs; k += gridDim.x) {
+    const uint64_t src = A.segs[k].src, dst = A.segs[k].dst, len = A.segs[k].len;
+    if (src > A.src_bytes || len > A.src_bytes - src || dst > A.dst_bytes || len > A.dst_bytes - dst) continue;
+    copy_span<NT>(A.dst + dst, A.src + src, len, A.src, A.src + A.src_bytes, threadIdx.x, blockDim.x);
+  }
+}
+
 // ---------------------------------------------------------------- K1
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // 8-byte aligned: one ds_read_b64
@@ -3509,6 +3568,13 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   hipStream_t st = l->st;
   if (F > out->files_cap) return fail(TSG_ERR_ARG, "batch has more files than its output buffers");
   if (total / C >= (1ull << 32) - 2) return fail(TSG_ERR_ARG, "batch too large for u32 chunk ids");
+  for (uint32_t k = 0; in.gather && k < in.ngather; k++) {  // nothing outside either buffer
+    const GatherSeg& g = in.gather[k];
+    if (g.src > in.src_bytes || g.len > in.src_bytes - g.src || g.dst > total || g.len > total - g.dst)
+      return fail(TSG_ERR_INTERNAL, "gather segment outside its buffers");
+  }
+  if (in.gather && in.ngather && (!in.dev_src || !in.gather_dev))
+    return fail(TSG_ERR_INTERNAL, "gather without a source");
   const uint64_t nchunks = (total + C - 1) / C;
   l->nchunks = nchunks;
   // K1F addresses the batch with 32-bit offsets (and its tiles past the end)
@@ -3568,7 +3634,16 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     HIP_TRY(hipMemcpyAsync(data, in.room, o_off + meta_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(out->ev[1], st));
   } else {
-    if (total && in.dev_src) {
+    if (in.gather) {
+      // spans of the caller's buffer: the kept files back to back into the lane buffer, in
+      // the stage's place and under its events (no launch for a batch without bytes)
+      if (in.ngather) {
+        GatherArgs GA{in.dev_src, in.src_bytes, data, total, in.gather_dev, in.ngather};
+        const int ggrid = (int)std::min<uint64_t>(in.ngather, (uint64_t)std::max(r->grid, 1));
+        gather_kernel<true><<<ggrid, 256, 0, st>>>(GA);
+        HIP_TRY(hipGetLastError());
+      }
+    } else if (total && in.dev_src) {
       // device-resident batch: HBM -> HBM on this lane's stream (one read and one write of the
       // batch; ev[0]..ev[1], the H2D's place, times it)
       const uint64_t words = (total + 15) / 16;
@@ -3903,11 +3978,15 @@ struct DeviceFetch {
   FetchSeg* segs = nullptr;  // pinned, host-mapped
   FetchSeg* segs_dev = nullptr;
   size_t segs_cap = 0;
+  GatherSeg* gsegs = nullptr;  // the same for fetch_gather
+  GatherSeg* gsegs_dev = nullptr;
+  size_t gsegs_cap = 0;
   ~DeviceFetch() {
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (st) (void)hipStreamSynchronize(st);
     if (segs) (void)hipHostFree(segs);
+    if (gsegs) (void)hipHostFree(gsegs);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
@@ -3958,6 +4037,61 @@ int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(f->ev[1], f->st));
   HIP_TRY(hipEventSynchronize(f->ev[1]));  // (a default event: the kernel's host writes are visible)
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  return TSG_OK;
+}
+
+int gate_spans(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, const uint64_t* starts_dev,
+               const uint64_t* lengths_dev, uint8_t* flags_dev, uint32_t nfiles, float* ms) {
+  *ms = 0;
+  if (!nfiles) return TSG_OK;
+  std::lock_guard<std::mutex> g(f->m);
+  HIP_TRY(hipSetDevice(f->d->device));
+  SpanGateArgs A{d_base, base_bytes, starts_dev, lengths_dev, flags_dev, nfiles};
+  const int grid = (int)std::min<uint64_t>(((uint64_t)nfiles + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  binary_gate_kernel<<<grid, 256, 0, f->st>>>(A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  HIP_TRY(hipEventSynchronize(f->ev[1]));  // (a default event: the flags are visible to the host)
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  return TSG_OK;
+}
+
+int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uint8_t* host_dst, uint64_t dst_bytes,
+                 const GatherSeg* segs, size_t nsegs, float* ms) {
+  *ms = 0;
+  if (!nsegs) return TSG_OK;
+  if (nsegs > 0xFFFFFFFFu) return fail(TSG_ERR_INTERNAL, "too many fetch segments");
+  for (size_t k = 0; k < nsegs; k++)  // the kernel writes host memory: nothing outside the mirror
+    if (segs[k].src > base_bytes || segs[k].len > base_bytes - segs[k].src || segs[k].dst > dst_bytes ||
+        segs[k].len > dst_bytes - segs[k].dst)
+      return fail(TSG_ERR_INTERNAL, "fetch segment outside its buffers");
+  std::lock_guard<std::mutex> g(f->m);
+  HIP_TRY(hipSetDevice(f->d->device));
+  if (f->gsegs_cap < nsegs) {
+    if (f->gsegs) HIP_TRY(hipHostFree(f->gsegs));
+    f->gsegs = nullptr;
+    f->gsegs_cap = 0;
+    const size_t cap = nsegs + nsegs / 2 + 1024;
+    HIP_TRY(hipHostMalloc((void**)&f->gsegs, sizeof(GatherSeg) * cap, hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&f->gsegs_dev, f->gsegs, 0));
+    f->gsegs_cap = cap;
+  }
+  std::memcpy(f->gsegs, segs, sizeof(GatherSeg) * nsegs);
+  GatherArgs A{};
+  A.src = d_base;
+  A.src_bytes = base_bytes;
+  HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
+  A.dst_bytes = dst_bytes;
+  A.segs = f->gsegs_dev;
+  A.nsegs = (uint32_t)nsegs;
+  const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  gather_kernel<false><<<grid, 256, 0, f->st>>>(A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  HIP_TRY(hipEventSynchronize(f->ev[1]));
   HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
   return TSG_OK;
 }

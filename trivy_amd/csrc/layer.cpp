@@ -596,6 +596,9 @@ void classify(const std::vector<TarEntry>& entries, size_t first, const Gate& g,
 
 namespace tsg {
 
+// utils.IsBinary for the other ingest paths (internal.hpp: the emulated gate of pipeline.cpp)
+bool is_binary_head(const uint8_t* p, uint64_t n) { return is_binary(p, (int64_t)std::min<uint64_t>(n, 300)); }
+
 struct SinkError {
   int rc;
   std::string msg;

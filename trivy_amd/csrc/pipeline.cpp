@@ -108,6 +108,19 @@ struct Batch {
   uint64_t fetched_files = 0, fetched_bytes = 0;
   bool whole_copy = false;
   double fetch_ms = 0;
+  // spans of a device buffer (tsg_device_spans_submit): dev_src is the buffer of base_bytes
+  // bytes (null when every span is empty), the batch is the kept files back to back, kept
+  // file f came from span_src[f], and the staging gather's segments lie in the slot's data
+  // area behind the mirror (pinned: the lane's gather_kernel reads them there)
+  bool spans = false;
+  uint64_t base_bytes = 0;
+  std::vector<uint64_t> span_src;
+  const GatherSeg* stage_segs = nullptr;
+  const GatherSeg* stage_segs_dev = nullptr;
+  uint32_t n_stage_segs = 0;
+  std::vector<uint8_t> emu_lane;  // emulated context: the gathered batch the kernels' emulation reads
+  double gate_ms = 0, gate_wait_ms = 0;
+  uint64_t files_in = 0, bytes_in = 0;
 };
 
 uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -151,6 +164,7 @@ struct tsg_ctx {
   // mirror (tsg_test_device_mirror)
   DeviceFetch* fetch = nullptr;
   tsg_device_input_stats dstats{};
+  tsg_device_spans_stats sstats{};
   int mirror_slot = -1;
   uint64_t mirror_take = 0;  // Slot::takes when the batch had it: a later taker overwrites the mirror
   uint64_t mirror_bytes = 0;
@@ -360,6 +374,61 @@ void update_stats(tsg_ctx* c, const Batch& b) {
   s.sum_resolve_ms += b.resolve_ms;
 }
 
+// The segment list of a gather: files are merged while each follows the last one in both the
+// caller's buffer and the destination, and every run is cut to kFetchSegBytes.
+struct GatherList {
+  std::vector<GatherSeg> segs;
+  GatherSeg run{0, 0, 0};
+  void add(uint64_t src, uint64_t dst, uint64_t len) {
+    if (!len) return;
+    if (run.len && run.src + run.len == src && run.dst + run.len == dst) {
+      run.len += len;
+      return;
+    }
+    flush();
+    run = GatherSeg{src, dst, len};
+  }
+  void flush() {
+    for (uint64_t a = 0; a < run.len; a += kFetchSegBytes)
+      segs.push_back(GatherSeg{run.src + a, run.dst + a, std::min(kFetchSegBytes, run.len - a)});
+    run.len = 0;
+  }
+};
+
+// The same for a batch given as spans of a device buffer: the source of file f is its span,
+// the destination its offset in the batch (the mirror is in the batch's coordinates).  With a
+// host rule every kept file is listed, still as segments: the source is not contiguous.
+void fetch_needed_spans(tsg_ctx* c, Batch* b, const BatchView& view, const KernelOutputView& kv) {
+  const Plan& plan = *c->rs->plan;
+  const uint32_t F = view.nfiles;
+  const uint64_t total = view.offsets[F];
+  uint8_t* mirror = const_cast<uint8_t*>(view.data);
+  const bool any_host = F && !host_rules(plan, kv).empty();
+  std::vector<uint8_t> has_cand(F, 0);
+  for (size_t i = 0; i < kv.ncand; i++)
+    if (kv.cand[i].file < F) has_cand[kv.cand[i].file] = 1;
+  GatherList gl;
+  for (uint32_t f = 0; f < F; f++) {
+    const uint64_t f0 = view.offsets[f], f1 = view.offsets[f + 1];
+    if (!file_needs_scan(plan, kv, f, has_cand[f] != 0, f0 == f1, any_host)) continue;
+    b->fetched_files++;
+    b->fetched_bytes += f1 - f0;
+    gl.add(b->span_src[f], f0, f1 - f0);
+  }
+  gl.flush();
+  for (const GatherSeg& s : gl.segs) b->segs.push_back({s.dst, s.len});
+  if (c->emulate) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (const GatherSeg& s : gl.segs) std::memcpy(mirror + s.dst, b->dev_src + s.src, s.len);
+    b->fetch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return;
+  }
+  float ms = 0;
+  if (fetch_gather(c->fetch, b->dev_src, b->base_bytes, mirror, total, gl.segs.data(), gl.segs.size(), &ms))
+    throw std::runtime_error(std::string("fetch of a spans batch failed: ") + tsg_last_error());
+  b->fetch_ms = ms;
+}
+
 // Device-resident batch, after its kernels: copy the files the resolver will read
 // (plan.hpp file_needs_scan, the resolver's own predicate) from the caller's buffer into
 // the batch's slot at their offsets.  The rest of the slot stays unwritten: resolve_batch
@@ -423,6 +492,26 @@ void update_device_stats(tsg_ctx* c, Batch* b) {
   d.sum_fetched_bytes += b->fetched_bytes;
   d.sum_stage_ms += b->t.h2d;
   d.sum_fetch_ms += b->fetch_ms;
+  if (b->spans) {
+    tsg_device_spans_stats& s = c->sstats;
+    s.gate_ms = b->gate_ms;
+    s.gather_ms = b->t.h2d;
+    s.wait_ms = b->gate_wait_ms;
+    s.files_in = b->files_in;
+    s.files_kept = b->nfiles;
+    s.files_dropped = b->files_in - b->nfiles;
+    s.bytes_in = b->bytes_in;
+    s.bytes_kept = b->bytes;
+    s.batches++;
+    s.sum_files_in += s.files_in;
+    s.sum_files_kept += s.files_kept;
+    s.sum_files_dropped += s.files_dropped;
+    s.sum_bytes_in += s.bytes_in;
+    s.sum_bytes_kept += s.bytes_kept;
+    s.sum_gate_ms += s.gate_ms;
+    s.sum_gather_ms += s.gather_ms;
+    s.sum_wait_ms += s.wait_ms;
+  }
   c->mirror_slot = (int)b->slot;
   c->mirror_take = c->slots[b->slot]->takes;
   c->mirror_bytes = b->bytes;
@@ -447,8 +536,16 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       eo.cand_cap = c->opt.cand_capacity;
       EmuStats es;
       BatchView kview = view;  // (a device-resident batch: the kernels read the caller's bytes)
-      if (b->dev_src) kview.data = b->dev_src;
+      if (b->spans) {  // the staging gather: the kept spans back to back, as the lane buffer holds them
+        b->emu_lane.resize((size_t)b->bytes);
+        for (uint32_t k = 0; k < b->n_stage_segs; k++)
+          std::memcpy(b->emu_lane.data() + b->stage_segs[k].dst, b->dev_src + b->stage_segs[k].src, b->stage_segs[k].len);
+        kview.data = b->emu_lane.data();
+      } else if (b->dev_src) {
+        kview.data = b->dev_src;
+      }
       emulate_kernels(*rs->plan, kview, c->opt.chunk_bytes, c->opt.ext_cap, &emu, nullptr, &eo, &es);
+      std::vector<uint8_t>().swap(b->emu_lane);
       kv = emu.view();
       auto u32 = [](uint64_t x) { return (uint32_t)std::min<uint64_t>(x, 0xFFFFFFFFu); };
       b->counts[kCntCand] = u32(es.candidates);
@@ -457,6 +554,9 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       b->counts[kCntEntries] = u32(es.layout.entries);
       b->counts[kCntSkipped] = u32(es.layout.skipped);
       b->cand_cap = c->opt.cand_capacity;
+    } else if (b->out < 0) {
+      // a spans batch whose files were all dropped: nothing was enqueued (submit_locked)
+      kv = KernelOutputView{};
     } else {
       if (hipEventSynchronize(ho.ev[kEvDone]) != hipSuccess) throw std::runtime_error("device batch failed");
       (void)batch_times(&ho, &b->t);
@@ -473,7 +573,8 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       kv.group_skipped = skipped ? ho.gskip : nullptr;
     }
     // a device-resident batch: the slot holds no content yet; fetch what the resolver reads
-    if (b->dev_src) fetch_needed(c, b.get(), view, kv);
+    if (b->spans) fetch_needed_spans(c, b.get(), view, kv);
+    else if (b->dev_src) fetch_needed(c, b.get(), view, kv);
     const auto t0 = std::chrono::steady_clock::now();
     resolve_batch(rs->rs, *rs->plan, view, kv, c->nt, &b->br);
     for (uint8_t st : b->br.status) b->files_found += st == kHasFindings;
@@ -495,7 +596,7 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
     c->slots[b->slot]->inflight--;
     if (b->out >= 0) c->out_busy[b->out] = 0;
     if (b->rc == TSG_OK) update_stats(c, *b);
-    if (b->rc == TSG_OK && b->dev_src) update_device_stats(c, b.get());
+    if (b->rc == TSG_OK && (b->dev_src || b->spans)) update_device_stats(c, b.get());
     c->cv.notify_all();
   }
   {
@@ -534,11 +635,11 @@ void job_worker(tsg_ctx* c) {
 // resolution itself fans out on the process-wide pool)
 int submit_locked(tsg_ctx* c, uint32_t sid, uint32_t nfiles, bool keep_result,
                   std::function<void(const std::shared_ptr<Batch>&)> on_done, std::shared_ptr<Batch>* out,
-                  const uint8_t* dev_src = nullptr) {
+                  const uint8_t* dev_src = nullptr, std::shared_ptr<Batch> spans = nullptr) {
   Slot& s = *c->slots[sid];
   int rc = check_layout(s, nfiles);
   if (rc) return rc;
-  auto b = std::make_shared<Batch>();
+  auto b = spans ? std::move(spans) : std::make_shared<Batch>();  // (a spans batch comes with its own fields set)
   b->slot = sid;
   b->nfiles = nfiles;
   b->bytes = s.off[nfiles];
@@ -548,15 +649,21 @@ int submit_locked(tsg_ctx* c, uint32_t sid, uint32_t nfiles, bool keep_result,
   BatchView view{s.data, s.off, nfiles, s.paths, s.poff};
   HostOut ho;
   std::shared_ptr<const std::vector<uint8_t>> kwu;
-  if (!c->emulate) {
+  if (!c->emulate && !(b->spans && nfiles == 0)) {  // (no launch for a spans batch without a kept file)
     if ((rc = out_take(c, nfiles, &b->out))) return rc;
     LaneState* l = c->lanes[c->seq++ % c->lanes.size()];
     ScanInput in = slot_input(s, nfiles);
-    if (dev_src) {  // the content comes from the caller's HBM; the slot's is fetched later
+    if (dev_src || b->spans) {  // the content comes from the caller's HBM; the slot's is fetched later
       in.data = nullptr;
       in.room = nullptr;
       in.room_bytes = 0;
       in.dev_src = dev_src;
+    }
+    if (b->spans) {
+      in.gather = b->stage_segs;
+      in.gather_dev = b->stage_segs_dev;
+      in.ngather = b->n_stage_segs;
+      in.src_bytes = b->base_bytes;
     }
     if ((rc = enqueue_scan(c->dr, l, in, &c->outs[b->out]))) {
       c->out_busy[b->out] = 0;
@@ -887,15 +994,17 @@ namespace tsg {
 namespace {
 // the slot's data must be visible to the device (fetch_kernel writes it): pinned memory of
 // the default kind is; if this runtime's is not, the buffer is allocated again as mapped
-int slot_map(Slot& s) {
+int slot_map(Slot& s, uint8_t** dev_data = nullptr) {
   void* dev = nullptr;
-  if (hipHostGetDevicePointer(&dev, s.data, 0) == hipSuccess && dev) return TSG_OK;
-  (void)hipGetLastError();
-  void* p = nullptr;
-  HIP_TRY(hipHostMalloc(&p, s.data_cap + slot_room_bytes(s.files_cap), hipHostMallocMapped));
-  (void)hipHostFree(s.data);
-  s.data = (uint8_t*)p;
-  HIP_TRY(hipHostGetDevicePointer(&dev, s.data, 0));
+  if (hipHostGetDevicePointer(&dev, s.data, 0) != hipSuccess || !dev) {
+    (void)hipGetLastError();
+    void* p = nullptr;
+    HIP_TRY(hipHostMalloc(&p, s.data_cap + slot_room_bytes(s.files_cap), hipHostMallocMapped));
+    (void)hipHostFree(s.data);
+    s.data = (uint8_t*)p;
+    HIP_TRY(hipHostGetDevicePointer(&dev, s.data, 0));
+  }
+  if (dev_data) *dev_data = (uint8_t*)dev;  // the device's address of s.data
   return TSG_OK;
 }
 
@@ -936,8 +1045,150 @@ int device_submit(tsg_ctx* c, const void* d_data, const uint64_t* offsets, uint3
   c->cv.notify_all();
   return rc;
 }
+
+// Files given as spans of one device buffer.  A slot sized for every listed byte (and, behind
+// that, for the gate's arrays and the staging segments: pinned memory the kernels read) is
+// taken; with the gate on, binary_gate_kernel decides IsBinary per span and this thread waits
+// for its flags (the call's only wait); the kept files' offsets and paths are written into
+// the slot as for any batch, the staging gather's segments behind its data, and the batch is
+// submitted with the gather in the stage's place.  kept[i] is final on return.
+int spans_submit(tsg_ctx* c, const void* d_base, uint64_t base_bytes, const uint64_t* starts, const uint64_t* lengths,
+                 uint32_t nfiles, const char* paths, const uint64_t* path_offsets, uint32_t flags, uint8_t* kept,
+                 std::shared_ptr<Batch>* out) {
+  if (flags & ~(uint32_t)TSG_SPANS_BINARY_GATE) return fail(TSG_ERR_ARG, "unknown flag bits");
+  if (nfiles && (!starts || !lengths || !path_offsets)) return fail(TSG_ERR_ARG, "bad argument");
+  uint64_t sum_in = 0;
+  for (uint32_t i = 0; i < nfiles; i++) {
+    if (starts[i] > base_bytes || lengths[i] > base_bytes - starts[i])
+      return fail(TSG_ERR_ARG, "span outside the buffer");
+    if (lengths[i] && !d_base) return fail(TSG_ERR_ARG, "bad argument");
+    if (__builtin_add_overflow(sum_in, lengths[i], &sum_in) || sum_in > (1ull << 48))
+      return fail(TSG_ERR_ARG, "the spans hold more bytes than a batch");
+  }
+  if (nfiles && path_offsets[0] != 0) return fail(TSG_ERR_ARG, "offsets[0] must be 0");
+  for (uint32_t i = 0; i < nfiles; i++)
+    if (path_offsets[i + 1] < path_offsets[i]) return fail(TSG_ERR_ARG, "offsets must be non-decreasing");
+  const uint64_t pbytes_in = nfiles ? path_offsets[nfiles] : 0;
+  if (pbytes_in && !paths) return fail(TSG_ERR_ARG, "bad argument");
+  // the slot's data area: [mirror of the kept files | staging segments | starts | lengths | flags]
+  const uint64_t seg_cap = (uint64_t)nfiles + sum_in / kFetchSegBytes + 1;
+  const uint64_t segs_at = round_up(sum_in, 16), starts_at = segs_at + sizeof(GatherSeg) * seg_cap,
+                 lengths_at = starts_at + 8ull * nfiles, flags_at = lengths_at + 8ull * nfiles;
+  uint32_t id;
+  Slot* sp;
+  {
+    std::unique_lock<std::mutex> lk(c->m);
+    int rc = slot_take(c, lk, kUpload, flags_at + nfiles, nfiles, pbytes_in, &id);
+    if (rc) return rc;
+    sp = c->slots[id].get();
+  }
+  Slot& s = *sp;  // ours alone until it is submitted
+  auto b = std::make_shared<Batch>();
+  b->spans = true;
+  b->base_bytes = base_bytes;
+  b->files_in = nfiles;
+  b->bytes_in = sum_in;
+  const uint8_t* base = (const uint8_t*)d_base;
+  uint8_t* data_dev = nullptr;
+  int rc = TSG_OK;
+  if (!c->emulate && hipSetDevice(c->device) != hipSuccess) rc = fail(TSG_ERR_GPU, "hipSetDevice failed");
+  if (!rc && !c->emulate) rc = slot_map(s, &data_dev);
+  uint8_t* binary = s.data + flags_at;
+  if (!rc) std::memset(binary, 0, nfiles);
+  if (!rc && nfiles && (flags & TSG_SPANS_BINARY_GATE)) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (c->emulate) {
+      for (uint32_t i = 0; i < nfiles; i++) binary[i] = lengths[i] && is_binary_head(base + starts[i], lengths[i]);
+      b->gate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+      std::memcpy(s.data + starts_at, starts, 8ull * nfiles);
+      std::memcpy(s.data + lengths_at, lengths, 8ull * nfiles);
+      float ms = 0;
+      rc = gate_spans(c->fetch, base, base_bytes, (const uint64_t*)(data_dev + starts_at),
+                      (const uint64_t*)(data_dev + lengths_at), data_dev + flags_at, nfiles, &ms);
+      b->gate_ms = ms;
+    }
+    b->gate_wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  uint32_t nkept = 0;
+  if (!rc) {
+    GatherList gl;
+    uint64_t at = 0, pat = 0;
+    s.off[0] = 0;
+    s.poff[0] = 0;
+    b->span_src.reserve(nfiles);
+    for (uint32_t i = 0; i < nfiles; i++) {
+      const bool keep = !binary[i];
+      if (kept) kept[i] = keep ? 1 : 0;
+      if (!keep) continue;
+      gl.add(starts[i], at, lengths[i]);
+      b->span_src.push_back(starts[i]);
+      at += lengths[i];
+      const uint64_t pn = path_offsets[i + 1] - path_offsets[i];
+      if (pn) std::memcpy(s.paths + pat, paths + path_offsets[i], pn);
+      pat += pn;
+      nkept++;
+      s.off[nkept] = at;
+      s.poff[nkept] = pat;
+    }
+    gl.flush();
+    if (gl.segs.size() > seg_cap) {
+      rc = fail(TSG_ERR_INTERNAL, "more staging segments than the slot holds");
+    } else {
+      if (!gl.segs.empty()) std::memcpy(s.data + segs_at, gl.segs.data(), sizeof(GatherSeg) * gl.segs.size());
+      b->stage_segs = (const GatherSeg*)(s.data + segs_at);
+      b->stage_segs_dev = data_dev ? (const GatherSeg*)(data_dev + segs_at) : nullptr;
+      b->n_stage_segs = (uint32_t)gl.segs.size();
+      if (knobs().device_poison.load()) {
+        const size_t n = sizeof(kPoisonLine) - 1;
+        for (uint64_t i = 0; i < at; i += n) std::memcpy(s.data + i, kPoisonLine, (size_t)std::min<uint64_t>(n, at - i));
+      }
+    }
+  }
+  std::lock_guard<std::mutex> g(c->m);
+  if (!rc) rc = submit_locked(c, id, nkept, false, nullptr, out, base, b);
+  s.owner = kFree;  // reusable once its submission is done
+  c->cv.notify_all();
+  return rc;
+}
 }  // namespace
 }  // namespace tsg
+
+int tsg_device_spans_submit(tsg_ctx* c, const void* d_base, uint64_t base_bytes, const uint64_t* starts,
+                            const uint64_t* lengths, uint32_t nfiles, const char* paths, const uint64_t* path_offsets,
+                            uint32_t flags, uint8_t* kept, uint64_t* ticket) {
+  if (!c || !ticket) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    std::shared_ptr<Batch> b;
+    int rc = spans_submit(c, d_base, base_bytes, starts, lengths, nfiles, paths, path_offsets, flags, kept, &b);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(c->m);
+    c->pending.emplace(b->ticket, b);
+    *ticket = b->ticket;
+    return TSG_OK;
+  });
+}
+
+int tsg_scan_device_spans(tsg_ctx* c, const void* d_base, uint64_t base_bytes, const uint64_t* starts,
+                          const uint64_t* lengths, uint32_t nfiles, const char* paths, const uint64_t* path_offsets,
+                          uint32_t flags, uint8_t* kept, tsg_result** out) {
+  if (!c || !out) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    std::shared_ptr<Batch> b;
+    int rc = spans_submit(c, d_base, base_bytes, starts, lengths, nfiles, paths, path_offsets, flags, kept, &b);
+    if (rc) return rc;
+    if ((rc = finish(b))) return rc;
+    *out = b->res.release();
+    return TSG_OK;
+  });
+}
+
+int tsg_ctx_get_device_spans_stats(const tsg_ctx* c, tsg_device_spans_stats* out) {
+  if (!c || !out) return fail(TSG_ERR_ARG, "bad argument");
+  std::lock_guard<std::mutex> g(c->m);
+  *out = c->sstats;
+  return TSG_OK;
+}
 
 int tsg_device_submit(tsg_ctx* c, const void* d_data, const uint64_t* offsets, uint32_t nfiles, const char* paths,
                       const uint64_t* path_offsets, uint64_t* ticket) {

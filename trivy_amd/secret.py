@@ -491,6 +491,7 @@ class GpuContext:
         self._fifo = []         # (ticket, paths) of this object's uncollected submissions
         self._paths = {}        # ticket -> paths
         self._tensors = {}      # ticket -> the tensor of a submit_tensor, alive until collect
+        self._kept = {}         # ticket -> the kept mask of a submit_spans, until collect
         self._device = int(device)
         self._emulate = bool(emulate)
 
@@ -510,6 +511,7 @@ class GpuContext:
         self._fifo = []
         self._paths = {}
         self._tensors = {}
+        self._kept = {}
         self._device = None     # (the owner knows; submit_tensor then only asks for a GPU tensor)
         self._emulate = False
         return self
@@ -628,6 +630,7 @@ class GpuContext:
             N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
         finally:
             self._tensors.pop(ticket, None)
+            self._kept.pop(ticket, None)
         return out
 
     def collect(self, ticket=None):
@@ -637,6 +640,7 @@ class GpuContext:
             N.check(N.lib().tsg_batch_collect(self._h, ticket, C.byref(out)))
         finally:
             self._tensors.pop(ticket, None)  # (a submit_tensor's tensor: the batch is done)
+            self._kept.pop(ticket, None)
         return self.scanner.decode(out, self._paths_of(paths))
 
     def pending(self):
@@ -653,9 +657,8 @@ class GpuContext:
         N.check(N.lib().tsg_scan_batch(self._h, *batch.ptrs(), C.byref(out)))
         return self.scanner.decode(out, self._paths_of(batch))
 
-    def _tensor_args(self, data, offsets, paths):
-        """Checked arguments of tsg_device_submit for a tensor: raises before any native
-        call.  Returns (pointer, offsets, nfiles, path bytes, path offsets, paths)."""
+    def _check_tensor(self, data):
+        """The tensor checks of the device-resident entry points (raise before any native call)."""
         import torch
         if not isinstance(data, torch.Tensor):
             raise TypeError("data must be a torch.Tensor, not %s" % type(data).__name__)
@@ -668,6 +671,29 @@ class GpuContext:
                 raise ValueError("an emulated context scans host tensors, not %s" % data.device)
         elif data.device.type != "cuda" or (self._device is not None and data.device.index != self._device):
             raise ValueError("data is on %s, the context on device %s" % (data.device, self._device))
+
+    @staticmethod
+    def _path_arrays(paths, nfiles):
+        paths = list(paths)
+        if len(paths) != nfiles:
+            raise ValueError("%d paths for %d files" % (len(paths), nfiles))
+        pb = [_b(p) for p in paths]
+        poffs = np.zeros(len(pb) + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(p) for p in pb], dtype=np.uint64), out=poffs[1:])
+        blob = np.frombuffer(b"".join(pb) or b"\0", dtype=np.uint8)
+        return paths, blob, poffs
+
+    @staticmethod
+    def _sync_tensor(data):
+        import torch
+        if data.device.type == "cuda":
+            # the bytes must be written when the library's own streams read them
+            torch.cuda.current_stream(data.device).synchronize()
+
+    def _tensor_args(self, data, offsets, paths):
+        """Checked arguments of tsg_device_submit for a tensor: raises before any native
+        call.  Returns (pointer, offsets, nfiles, path bytes, path offsets, paths)."""
+        self._check_tensor(data)
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         if offs.ndim != 1 or len(offs) < 1 or int(offs[0]) != 0:
             raise ValueError("offsets must be 1-D and start at 0")
@@ -675,19 +701,39 @@ class GpuContext:
             raise ValueError("offsets must be non-decreasing")
         if int(offs[-1]) > data.numel():
             raise ValueError("offsets cover %d bytes, the tensor holds %d" % (int(offs[-1]), data.numel()))
-        paths = list(paths)
-        if len(paths) != len(offs) - 1:
-            raise ValueError("%d paths for %d files" % (len(paths), len(offs) - 1))
-        pb = [_b(p) for p in paths]
-        poffs = np.zeros(len(pb) + 1, dtype=np.uint64)
-        np.cumsum(np.array([len(p) for p in pb], dtype=np.uint64), out=poffs[1:])
-        blob = np.frombuffer(b"".join(pb) or b"\0", dtype=np.uint8)
-        if data.device.type == "cuda":
-            # the bytes must be written when the library's own streams read them
-            torch.cuda.current_stream(data.device).synchronize()
+        paths, blob, poffs = self._path_arrays(paths, len(offs) - 1)
+        self._sync_tensor(data)
         u64p = C.POINTER(C.c_uint64)
         return (C.c_void_p(data.data_ptr() if data.numel() else None), offs.ctypes.data_as(u64p),
-                C.c_uint32(len(pb)), C.c_void_p(blob.ctypes.data), poffs.ctypes.data_as(u64p)), (offs, blob, poffs), paths
+                C.c_uint32(len(paths)), C.c_void_p(blob.ctypes.data), poffs.ctypes.data_as(u64p)), (offs, blob, poffs), paths
+
+    def _spans_args(self, data, starts, lengths, paths, binary_gate):
+        """Checked arguments of tsg_device_spans_submit (raises before any native call):
+        (arguments up to `kept`, arrays to keep alive, paths, kept mask)."""
+        self._check_tensor(data)
+
+        def u64(a, what):
+            a = np.asarray(a)
+            if a.ndim != 1:
+                raise ValueError("%s must be 1-D" % what)
+            if a.size and (a.dtype.kind not in "iu" or (a.dtype.kind == "i" and (a < 0).any())):
+                raise ValueError("%s must be non-negative integers" % what)
+            return np.ascontiguousarray(a, dtype=np.uint64)
+        st, ln = u64(starts, "starts"), u64(lengths, "lengths")
+        if len(st) != len(ln):
+            raise ValueError("%d starts for %d lengths" % (len(st), len(ln)))
+        n = data.numel()
+        n64 = np.uint64(n)
+        if ((st > n64) | (ln > n64 - np.minimum(st, n64))).any():
+            raise ValueError("a span lies outside the tensor's %d bytes" % n)
+        paths, blob, poffs = self._path_arrays(paths, len(st))
+        self._sync_tensor(data)
+        kept = np.zeros(max(len(st), 1), dtype=np.uint8)
+        u64p = C.POINTER(C.c_uint64)
+        args = (C.c_void_p(data.data_ptr() if n else None), C.c_uint64(n), st.ctypes.data_as(u64p),
+                ln.ctypes.data_as(u64p), C.c_uint32(len(st)), C.c_void_p(blob.ctypes.data), poffs.ctypes.data_as(u64p),
+                C.c_uint32(N.TSG_SPANS_BINARY_GATE if binary_gate else 0), kept.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return args, (st, ln, blob, poffs), paths, kept[:len(st)]
 
     def submit_tensor(self, data, offsets, paths):
         """tsg_device_submit: scan files that already live in this device's memory.  data is a
@@ -711,6 +757,45 @@ class GpuContext:
         N.check(N.lib().tsg_scan_device(self._h, *args, C.byref(out)))
         del keep
         return self.scanner.decode(out, paths)
+
+    def submit_spans(self, data, starts, lengths, paths, binary_gate=True):
+        """tsg_device_spans_submit: scan files given as spans of one tensor on the context's
+        device: file i = data[starts[i]:starts[i] + lengths[i]], in any order, with gaps (a
+        layer tar as a GPU decompressor leaves it).  With binary_gate the files
+        utils.IsBinary calls binary are dropped on the device.  The tensor is kept alive, and
+        must stay unchanged, until collect(ticket), which returns the KEPT files' findings in
+        input order.  Returns the ticket; spans_kept(ticket) is the kept mask over the input
+        files, final as soon as this returns."""
+        args, keep, paths, kept = self._spans_args(data, starts, lengths, paths, binary_gate)
+        t = C.c_uint64()
+        N.check(N.lib().tsg_device_spans_submit(self._h, *args, C.byref(t)))
+        del keep
+        kept = kept.astype(bool)
+        with self._lock:
+            self._tensors[t.value] = data
+            self._kept[t.value] = kept
+        return self._track(t.value, [p for p, k in zip(paths, kept) if k])
+
+    def spans_kept(self, ticket):
+        """The kept mask of a submit_spans that is not collected yet (True = scanned)."""
+        with self._lock:
+            return self._kept[ticket]
+
+    def scan_spans(self, data, starts, lengths, paths, binary_gate=True):
+        """tsg_scan_device_spans: submit_spans + collect in one thread-safe call.  Returns
+        (results of the kept files in input order, kept mask over the input files)."""
+        args, keep, paths, kept = self._spans_args(data, starts, lengths, paths, binary_gate)
+        out = C.c_void_p()
+        N.check(N.lib().tsg_scan_device_spans(self._h, *args, C.byref(out)))
+        del keep
+        kept = kept.astype(bool)
+        return self.scanner.decode(out, [p for p, k in zip(paths, kept) if k]), kept
+
+    def device_spans_stats(self):
+        """tsg_device_spans_stats of the context's spans batches."""
+        s = N.DeviceSpansStats()
+        N.check(N.lib().tsg_ctx_get_device_spans_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in N.DeviceSpansStats._fields_}
 
     def stats(self):
         s = N.Stats()
