@@ -669,6 +669,64 @@ int tsg_fs_scan(tsg_ctx* ctx, const char* root, const char* const* skip_files, u
                 tsg_layer** layer, tsg_result** out);
 void tsg_layer_free(tsg_layer* layer);
 
+/* -- Device-resident input, a whole layer tar ------------------------------------------
+ * tsg_layer_scan for an uncompressed layer tar that lies in this GPU's memory (what a GPU
+ * decompressor leaves behind): d_tar is a device pointer on the context's device, any
+ * alignment, tar_len bytes.  One kernel (tar_mark_kernel) reads the tar once and marks, per
+ * 512-byte block, whether it passes archive/tar's header checksum and whether it is all
+ * zero; the two bitmaps come back in one copy.  Every marked block (512 bytes each) is
+ * gathered into pinned memory, and archive/tar's Reader.Next walks the header chain on the
+ * host over that sparse view: a position whose block is marked is read from the gathered
+ * copy, an all-zero block is a zero block, anything else is "invalid header" -- what the
+ * checksum test gives on the full bytes.  Blocks inside a member's data that happen to
+ * checksum (a tar stored in the tar) are fetched and never reached.  The payloads of PAX 'x'
+ * and GNU 'L' / 'K' headers are gathered in rounds: the chain is walked with the headers'
+ * own sizes, the extended headers met are fetched in one launch, and the walk is repeated
+ * until it needed nothing it did not have (an ordinary tar: one round, or none).  The
+ * walker's whiteout / skip logic and SecretAnalyzer.Required then run on the host as in
+ * tsg_layer_scan; the kept entries go, in walk order and in batches cut like
+ * tsg_layer_scan's pieces, through tsg_device_spans_submit with TSG_SPANS_BINARY_GATE,
+ * several batches in flight.  So only the header blocks, the extended-header payloads, the
+ * bitmaps (2 bits per block) and the files the resolver reads cross PCIe.
+ * *layer and *out are what tsg_layer_scan returns for the same bytes in host memory, field
+ * for field (the layer's data view is NULL: the files are not packed on the host); a
+ * malformed archive fails with TSG_ERR_ARG and the same "failed to extract the archive: ..."
+ * text.  TSG_ERR_ARG too: NULL ctx, layer or out; NULL d_tar with tar_len > 0.  The context
+ * keeps working after an error.  Thread-safe against other submitters on the context; the
+ * caller leaves the buffer untouched until the call returns.  Under TSG_CTX_EMULATE d_tar is
+ * a host pointer, the marks are a CPU loop and the gathers memcpy of the same lists. */
+int tsg_device_layer_scan(tsg_ctx* ctx, const void* d_tar, uint64_t tar_len,
+                          const char* const* skip_files, uint32_t n_skip_files,
+                          const char* const* skip_dirs, uint32_t n_skip_dirs,
+                          const char* config_path, tsg_layer** layer, tsg_result** out);
+typedef struct tsg_device_layer_stats {
+  /* last successful tsg_device_layer_scan */
+  double mark_ms;            /* tar_mark_kernel by HIP events (wall time when emulated) */
+  uint64_t tar_bytes;
+  uint64_t blocks;           /* whole 512-byte blocks of the tar */
+  uint64_t marked_blocks;    /* blocks that pass the header checksum */
+  uint64_t chain_entries;    /* members on the header chain (after extended headers are applied) */
+  uint64_t header_bytes;     /* header blocks fetched: 512 * marked_blocks */
+  uint64_t payloads;         /* extended-header payloads fetched */
+  uint64_t payload_bytes;
+  uint64_t payload_rounds;   /* gather launches for them */
+  uint64_t span_batches;     /* tsg_device_spans_submit batches */
+  uint64_t files_scanned;    /* files in the result (Required and not binary) */
+  uint64_t fetched_bytes;    /* files the batches' resolvers read (tsg_device_input_stats.fetched_bytes) */
+  uint64_t pcie_bytes;       /* header_bytes + payload_bytes + fetched_bytes */
+  /* all successful calls so far */
+  uint64_t calls, sum_tar_bytes, sum_blocks, sum_marked_blocks, sum_chain_entries, sum_header_bytes,
+      sum_payloads, sum_payload_bytes, sum_payload_rounds, sum_span_batches, sum_files_scanned,
+      sum_fetched_bytes, sum_pcie_bytes;
+  double sum_mark_ms;
+} tsg_device_layer_stats;
+int tsg_ctx_get_device_layer_stats(const tsg_ctx* ctx, tsg_device_layer_stats* out);
+/* Test hook: the two bitmaps as tar_mark_kernel (or its emulation) leaves them for the
+ * tar_len bytes at d_tar: bit b % 64 of word b / 64 belongs to block b, (tar_len / 512 + 63)
+ * / 64 words each; words_cap is the room of both arrays (TSG_ERR_ARG if it is too small). */
+int tsg_test_device_tar_marks(tsg_ctx* ctx, const void* d_tar, uint64_t tar_len,
+                              uint64_t* header_bits, uint64_t* zero_bits, uint64_t words_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 
     python tools/device_bench.py [--gb 4] [--steps 20] [--rounds 3] [--warmup 1] [--depth 4]
     python tools/device_bench.py --spans [--gb 1] [--batch-mib 256] ...
+    python tools/device_bench.py --layer [--gb 1] [--steps 5] [--rounds 3] ...
 
 The configs[1] workload of bench.py (builtin rules over the seeded corpus, seed 2, in
 batches of --batch-mib) is scanned two ways on one GpuContext:
@@ -35,7 +36,22 @@ context, over the same kept bytes:
 Every batch's result bytes of the two paths are compared, and the kept mask is compared
 with IsBinary on the host.  The JSON line carries GB/s of kept bytes of both paths per
 window, and per batch the gate, the submit wait and the gather beside the compact path's
-stage_ms, each as the mean of every window (so the spread between windows shows)."""
+stage_ms, each as the mean of every window (so the spread between windows shows).
+
+--layer measures tsg_device_layer_scan (walker.scan_layer_tensor).  One configs.layer_tar
+layer of --gb GiB is scanned two ways on one context, in alternating windows:
+
+  host      the tar in host memory through tsg_layer_scan (walker.scan_layer_pipelined): the
+            only way to scan these bytes without the new call; the kept files cross PCIe
+  device    the same bytes uploaded once as one tensor, through tsg_device_layer_scan: the
+            marks kernel over the whole tar, the header blocks and extended-header payloads
+            fetched, the walk on the host, the kept files as spans batches
+
+Both are timed as raw native calls (nothing is decoded in Python inside a window), and the
+result bytes, paths, opaque dirs, whiteouts and walked count of the two calls are compared.  The JSON line carries GB/s of tar of both
+per window, mark_ms per window beside the staging copy of the same number of bytes
+(stage_ms of a scan_tensor over as many zero bytes as one file, a single read + write
+pass), the header and payload bytes fetched, and the share of the tar that crossed PCIe."""
 import argparse
 import collections
 import ctypes as C
@@ -64,9 +80,14 @@ def main():
     ap.add_argument("--spans", action="store_true",
                     help="files as spans of one buffer with 30 %% binary blobs against scan_tensor "
                          "over the pre-compacted kept bytes")
+    ap.add_argument("--layer", action="store_true",
+                    help="one layer tar from host memory (tsg_layer_scan) against the same tar in a tensor "
+                         "(tsg_device_layer_scan)")
     args = ap.parse_args()
     if args.spans:
         return main_spans(args)
+    if args.layer:
+        return main_layer(args)
 
     import numpy as np
     import torch
@@ -345,6 +366,96 @@ def main_spans(args):
     ctx.close()
     print(json.dumps(line))
     return 0 if equal and kept_equal else 1
+
+
+def main_layer(args):
+    import numpy as np
+    import torch
+    from trivy_amd import configs
+    from trivy_amd import secret as S
+
+    def log(msg):
+        print(msg, file=sys.stderr, flush=True)
+
+    sc = S.NewScanner(None)
+    t0 = time.perf_counter()
+    tar = configs.layer_tar(int(args.gb * (1 << 30)), seed=args.seed)
+    log("layer tar %.3f GiB, built in %.1fs" % (len(tar) / (1 << 30), time.perf_counter() - t0))
+    dev = "cpu" if args.emulate else "cuda:%d" % args.device
+    whole = torch.from_numpy(np.frombuffer(tar, dtype=np.uint8).copy()).to(dev)
+    if not args.emulate:
+        torch.cuda.synchronize()
+    ctx = S.GpuContext(sc, args.device, emulate=args.emulate)
+
+    def sums(d):
+        return {k: v for k, v in d.items() if k.startswith("sum_") or k in ("batches", "calls")}
+
+    def timed(scan):
+        for _ in range(args.warmup):
+            scan()
+        l0, d0 = sums(ctx.device_layer_stats()), sums(ctx.device_input_stats())
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            got = scan()
+        dt = time.perf_counter() - t0
+        l1, d1 = sums(ctx.device_layer_stats()), sums(ctx.device_input_stats())
+        return got, dt, {k: l1[k] - l0[k] for k in l1}, {k: d1[k] - d0[k] for k in d1}
+
+    from trivy_amd import _native as N
+    L = N.lib()
+    host = np.frombuffer(tar, dtype=np.uint8)
+    ctx._check_tensor(whole)
+
+    def raw(call, ptr):
+        """One native call; (result bytes, path bytes, path offsets, opq, wh, walked): nothing is
+        decoded in Python inside the timed windows."""
+        h, out = C.c_void_p(), C.c_void_p()
+        N.check(call(ctx.handle, C.c_void_p(ptr), len(tar), None, 0, None, 0, b"", C.byref(h), C.byref(out)))
+        v = N.LayerView()
+        N.check(L.tsg_layer_get(h, C.byref(v)))
+        n = C.c_size_t()
+        p = L.tsg_result_data(out, C.byref(n))
+        poffs = np.ctypeslib.as_array(v.path_offsets, shape=(v.nfiles + 1,)).copy()
+        got = (C.string_at(p, n.value), C.string_at(v.paths, int(poffs[-1])), poffs.tobytes(),
+               C.string_at(v.opq, v.opq_len), C.string_at(v.wh, v.wh_len), v.walked)
+        L.tsg_result_free(out)
+        L.tsg_layer_free(h)
+        return got
+
+    hg, dg, marks, equal = [], [], [], True
+    for _ in range(max(1, args.rounds)):
+        want, hdt, _, _ = timed(lambda: raw(L.tsg_layer_scan, host.ctypes.data))
+        got, ddt, dl, dd = timed(lambda: raw(L.tsg_device_layer_scan, whole.data_ptr()))
+        equal = equal and got == want
+        hg.append(round(len(tar) * args.steps / hdt / 1e9, 3))
+        dg.append(round(len(tar) * args.steps / ddt / 1e9, 3))
+        marks.append(round(dl["sum_mark_ms"] / max(1, dl["calls"]), 4))
+    st = ctx.device_layer_stats()
+    # a plain copy pass over as many bytes: the staging kernel of scan_tensor, the tar as one file
+    # (a batch addresses 4 GiB at most: a longer tar is cut to that, and the time scaled)
+    n1 = min(len(tar), (1 << 32) - (1 << 20))
+    blank = torch.zeros(n1, dtype=torch.uint8, device=dev)  # (zero bytes: nothing to resolve or fetch)
+    for _ in range(2):
+        ctx.scan_tensor(blank, np.array([0, n1], dtype=np.uint64), ["/whole.bin"])
+    stage_ms = ctx.device_input_stats()["stage_ms"] * len(tar) / n1
+    line = {
+        "metric": "secret-scan GB/s of tar (builtin rules), a layer tar in GPU memory (tsg_device_layer_scan) vs the "
+                  "same tar from host memory (tsg_layer_scan), 1 MI355X",
+        "device_gbs": round(float(np.median(dg)), 3), "host_gbs": round(float(np.median(hg)), 3), "unit": "GB/s",
+        "device_gbs_windows": dg, "host_gbs_windows": hg, "outputs_equal": equal,
+        "tar_gib": round(len(tar) / (1 << 30), 3), "steps": args.steps, "rounds": args.rounds, "warmup": args.warmup,
+        "mark_ms_windows": marks, "mark_ms": round(float(np.median(marks)), 4),
+        "mark_read_gbs": round(len(tar) / max(float(np.median(marks)), 1e-9) / 1e6, 1),
+        "stage_ms_same_bytes": round(stage_ms, 4),
+        "last_call": {k: st[k] for k in ("blocks", "marked_blocks", "chain_entries", "header_bytes", "payloads",
+                                         "payload_bytes", "payload_rounds", "span_batches", "files_scanned",
+                                         "fetched_bytes", "pcie_bytes")},
+        "pcie_share": round(st["pcie_bytes"] / max(1, len(tar)), 5),
+        "files_walked": want[5],
+    }
+    ctx.close()
+    print(json.dumps(line))
+    return 0 if equal else 1
 
 
 if __name__ == "__main__":

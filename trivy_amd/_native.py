@@ -113,6 +113,18 @@ class DeviceSpansStats(C.Structure):
 
 TSG_SPANS_BINARY_GATE = 1
 
+
+class DeviceLayerStats(C.Structure):
+    """tsg_device_layer_stats, in the header's order."""
+    _fields_ = [("mark_ms", C.c_double)] + [(k, C.c_uint64) for k in (
+        "tar_bytes", "blocks", "marked_blocks", "chain_entries", "header_bytes", "payloads",
+        "payload_bytes", "payload_rounds", "span_batches", "files_scanned", "fetched_bytes",
+        "pcie_bytes", "calls", "sum_tar_bytes", "sum_blocks", "sum_marked_blocks",
+        "sum_chain_entries", "sum_header_bytes", "sum_payloads", "sum_payload_bytes",
+        "sum_payload_rounds", "sum_span_batches", "sum_files_scanned", "sum_fetched_bytes",
+        "sum_pcie_bytes")] + [("sum_mark_ms", C.c_double)]
+
+
 # (name, restype, argtypes) -- every symbol include/trivy_secret.h declares
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
@@ -152,6 +164,11 @@ SIGNATURES = [
     ("tsg_scan_device_spans", C.c_int, [_P, _P, C.c_uint64, _U64P, _U64P, C.c_uint32, _P, _U64P, C.c_uint32,
                                         _U8P, C.POINTER(_P)]),
     ("tsg_ctx_get_device_spans_stats", C.c_int, [_P, C.POINTER(DeviceSpansStats)]),
+    ("tsg_device_layer_scan", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32,
+                                        C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(_P),
+                                        C.POINTER(_P)]),
+    ("tsg_ctx_get_device_layer_stats", C.c_int, [_P, C.POINTER(DeviceLayerStats)]),
+    ("tsg_test_device_tar_marks", C.c_int, [_P, _P, C.c_uint64, _U64P, _U64P, C.c_uint64]),
     ("tsg_slot_acquire", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(SlotView)]),
     ("tsg_slot_submit", C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P]),
     ("tsg_slot_release", C.c_int, [_P, C.c_uint32]),

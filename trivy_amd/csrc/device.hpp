@@ -202,6 +202,12 @@ int gate_spans(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, const
 // host_dst is pinned, device-visible memory of dst_bytes bytes.  Synchronous, as fetch_segments.
 int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uint8_t* host_dst, uint64_t dst_bytes,
                  const GatherSeg* segs, size_t nsegs, float* ms);
+// A layer tar in device memory: tar_mark_kernel's two bitmaps over the whole 512-byte blocks
+// of the tar_len bytes at d_tar (any alignment), bit b % 64 of word b / 64 for block b.
+// marks[0, words) = the block passes archive/tar's header checksum, marks[words, 2 * words) =
+// the block is all zero, words = (tar_len / 512 + 63) / 64; both come back in one D2H.
+// Synchronous; *ms = the kernel's HIP-event time.
+int mark_tar(DeviceFetch* f, const uint8_t* d_tar, uint64_t tar_len, uint64_t* marks, float* ms);
 // the whole batch in one runtime D2H (every file is needed)
 int fetch_whole(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, float* ms);
 

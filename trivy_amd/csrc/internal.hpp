@@ -6,6 +6,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/trivy_secret.h"
 #include "plan.hpp"
@@ -29,6 +30,31 @@ const tsg_ruleset* ctx_ruleset(const tsg_ctx* c);
 uint64_t ctx_slot_bytes(const tsg_ctx* c);
 // utils.IsBinary (utils.go:71-89) of a file of n bytes at p: layer.cpp's is_binary
 bool is_binary_head(const uint8_t* p, uint64_t n);
+
+
+// ---- a layer tar in device memory (tsg_device_layer_scan): layer.cpp drives the walk,
+// pipeline.cpp owns the device.  Under TSG_CTX_EMULATE the "device" pointer is a host pointer.
+// archive/tar's header checksum test and the all-zero test of one 512-byte block (layer.cpp)
+void tar_block_marks(const uint8_t* block, bool* header, bool* zero);
+// the two bitmaps of tar_mark_kernel (device.hpp mark_tar) or of their emulation:
+// marks[0, words) header bits, marks[words, 2 * words) zero bits, words = (tar_len / 512 + 63) / 64
+int ctx_tar_marks(tsg_ctx* c, const void* d_tar, uint64_t tar_len, uint64_t* marks, double* ms);
+// A buffer of the context's small pool of pinned, device-visible memory (plain memory when
+// emulated); ctx_fetch_ranges grows it.  Given back with ctx_pin_give (reused by later calls).
+struct PinBuf {
+  uint8_t* p = nullptr;
+  uint64_t cap = 0;
+};
+void ctx_pin_give(tsg_ctx* c, PinBuf* b);
+// dst->p = the listed {offset, length} ranges of the base_bytes bytes at d_base, back to back
+// in list order (gather_kernel: adjacent ranges merge, segments are cut to kFetchSegBytes;
+// memcpy of the same segments when emulated).  Every range lies inside the buffer.
+int ctx_fetch_ranges(tsg_ctx* c, const void* d_base, uint64_t base_bytes,
+                     const std::pair<uint64_t, uint64_t>* ranges, size_t n, PinBuf* dst);
+// tsg_batch_collect of a device-resident batch, and the bytes its fetch brought to the host
+int ctx_collect_device(tsg_ctx* c, uint64_t ticket, tsg_result** out, uint64_t* fetched_bytes);
+// one finished tsg_device_layer_scan: `last` holds the call's fields; the sums are kept here
+void ctx_device_layer_done(tsg_ctx* c, const tsg_device_layer_stats& last);
 
 // test and measurement knobs (knobs.cpp, tsg_test_knob); 0 = default
 struct Knobs {

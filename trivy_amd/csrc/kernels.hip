@@ -416,6 +416,145 @@ __global__ void __launch_bounds__(256) gather_kernel(GatherArgs A) {
   }
 }
 
+// A layer tar that lies in device memory (tsg_device_layer_scan): tar_mark_kernel is the one
+// pass over all of it.  For every whole 512-byte block b of the tar it decides
+//   header[b]: archive/tar's checksum test (layer.cpp checksum_ok): the field at 148..155
+//              parses as a number (octal with spaces / NULs trimmed, or GNU base-256) and
+//              equals the unsigned or the signed sum of the block's bytes, the field itself
+//              counted as eight spaces;
+//   zero[b]:   all 512 bytes are 0.
+// A pure map over blocks: no size field is followed, so malformed input changes bits, never
+// addresses.  A wave owns 64 consecutive blocks = one word of each bitmap, which its lane 0
+// stores once.  It sums them two at a time, a block per 32-lane half and 16 bytes per lane:
+// lane k of a half loads the 16-B aligned word k of the block's aligned window (the tar
+// starts at any byte: with a = its address mod 16, the block's bytes are bytes [a, a + 512)
+// of 33 such words, and lane 0 of the half also takes word 32 and masks both ends), so a
+// wave's load is 1 KiB contiguous.  A word that reaches outside the tar is put together from
+// the byte loads of its bytes inside it, so nothing outside [tar, tar + len) is read.  The
+// sums of all 512 bytes (unsigned, and the count of bytes >= 0x80, in one register) fold over
+// the half with five xor-shuffles; they and the three dwords that hold the field are handed
+// to lane j of the wave for block j.  After the 64 blocks every lane decides its own block
+// once: the field's bytes leave the sums, the field is parsed, and two ballots are the words.
+struct TarMarkArgs {
+  const uint8_t* tar;    // any alignment
+  uint64_t len;          // bytes; the tail under 512 belongs to no block
+  uint64_t* header;      // [words] device memory
+  uint64_t* zero;        // [words]
+  uint64_t nblocks, words;
+};
+
+// keep the bytes i of a 16-byte word with lo <= i < hi (0 <= lo <= hi <= 16)
+__device__ __forceinline__ c_u32x4 keep_bytes16(c_u32x4 v, uint32_t lo, uint32_t hi) {
+  const uint32_t en = ((1u << hi) - 1u) & ~((1u << lo) - 1u);  // a bit per byte
+  // 4 byte-enable bits -> 0xFF per enabled byte
+  auto spread4 = [](uint32_t nib) { return (((nib & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu; };
+  v.x &= spread4(en), v.y &= spread4(en >> 4), v.z &= spread4(en >> 8), v.w &= spread4(en >> 12);
+  return v;
+}
+
+// the aligned 16 bytes at q, with 0 for the bytes outside [lo, hi)
+__device__ __forceinline__ c_u32x4 load16_inside(const uint8_t* q, const uint8_t* lo, const uint8_t* hi) {
+  if (q >= lo && q + 16 <= hi) return *(const c_u32x4*)q;
+  uint32_t x[4] = {0, 0, 0, 0};
+  for (int i = 0; i < 16; i++)
+    if (q + i >= lo && q + i < hi) x[i >> 2] |= (uint32_t)q[i] << (8 * (i & 3));
+  c_u32x4 v;
+  v.x = x[0], v.y = x[1], v.z = x[2], v.w = x[3];
+  return v;
+}
+
+// acc + (sum of the 16 bytes | count of the bytes >= 0x80 << 20)
+__device__ __forceinline__ uint32_t tar_sums16(c_u32x4 v, uint32_t acc) {
+  acc = __builtin_amdgcn_sad_u8(v.x, 0u, acc);
+  acc = __builtin_amdgcn_sad_u8(v.y, 0u, acc);
+  acc = __builtin_amdgcn_sad_u8(v.z, 0u, acc);
+  acc = __builtin_amdgcn_sad_u8(v.w, 0u, acc);
+  const uint32_t neg = __popc(v.x & 0x80808080u) + __popc(v.y & 0x80808080u) + __popc(v.z & 0x80808080u) +
+                       __popc(v.w & 0x80808080u);
+  return acc + (neg << 20);
+}
+
+// layer.cpp parse_num of the 8-byte checksum field f (f[0] = the low byte of lo)
+__device__ __forceinline__ bool tar_chksum_field(uint32_t lo, uint32_t hi, uint64_t* out) {
+  const uint64_t f = (uint64_t)hi << 32 | lo;
+  auto at = [&](int i) { return (uint32_t)(f >> (8 * i)) & 0xFFu; };  // (a shift, not an indexed array)
+  if (at(0) & 0x80) {  // GNU base-256
+    if (at(0) & 0x40) return false;  // negative
+    uint64_t v = at(0) & 0x7f;
+    for (int i = 1; i < 8; i++) {
+      if (v >> 55) return false;
+      v = (v << 8) | at(i);
+    }
+    *out = v;
+    return true;
+  }
+  int a = 0, b = 8;
+  while (a < b && (at(a) == ' ' || at(a) == 0)) a++;
+  while (b > a && (at(b - 1) == ' ' || at(b - 1) == 0)) b--;
+  uint64_t v = 0;
+  bool ok = true;
+  for (int i = a; i < b; i++) {
+    ok &= at(i) >= '0' && at(i) <= '7';
+    v = v * 8 + (uint64_t)(at(i) - '0');
+  }
+  *out = v;
+  return ok;
+}
+
+__global__ void __launch_bounds__(256) tar_mark_kernel(TarMarkArgs A) {
+  const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64, half = lane >> 5, k = lane & 31u;
+  const uint8_t* const hi = A.tar + A.len;
+  const uint32_t a = (uint32_t)((uintptr_t)A.tar & 15);  // (512 | block stride: the same for every block)
+  // the field's bytes 148..155 are bytes r.. of dwords d0, d0 + 1, d0 + 2 of the window:
+  // dword d is component d & 3 of lane d >> 2 of the half
+  const uint32_t d0 = (148 + a) >> 2, r = (148 + a) & 3u;
+  const uint32_t from = (lane & 1u) * 32;  // lane j takes block j from half j & 1
+  for (uint64_t w = (uint64_t)blockIdx.x * wpb + threadIdx.x / 64; w < A.words; w += (uint64_t)gridDim.x * wpb) {
+    const uint32_t nb = (uint32_t)min<uint64_t>(64, A.nblocks - w * 64);  // (uniform over the wave)
+    uint32_t my_acc = 0, my_f[3] = {0, 0, 0};  // of block 64 w + lane
+    for (uint32_t j = 0; j < nb; j += 2) {
+      uint32_t acc = 0;  // sum of the bytes | count of the bytes >= 0x80 << 20
+      c_u32x4 mine{0, 0, 0, 0};
+      if (j + half < nb) {
+        const uint8_t* const q = A.tar + (w * 64 + j + half) * 512 - a + 16 * k;  // word k of the window
+        mine = load16_inside(q, A.tar, hi);
+        if (a && k == 0) mine = keep_bytes16(mine, a, 16);  // (its first bytes belong to the block before)
+        acc = tar_sums16(mine, 0);
+        if (a && k == 0)  // word 32: the block's last a bytes
+          acc = tar_sums16(keep_bytes16(load16_inside(q + 512, A.tar, hi), 0, a), acc);
+      }
+      for (int s = 16; s; s >>= 1) acc += __shfl_xor(acc, s);  // (stays inside the 32-lane half)
+      const uint32_t tot = __shfl(acc, (int)from);
+      uint32_t fv[3];
+      for (uint32_t t = 0; t < 3; t++) {
+        const uint32_t d = d0 + t, c = d & 3u;
+        const uint32_t sel = c == 0 ? mine.x : c == 1 ? mine.y : c == 2 ? mine.z : mine.w;
+        fv[t] = __shfl(sel, (int)(from + (d >> 2)));
+      }
+      if ((lane & ~1u) == j) {
+        my_acc = tot;
+        my_f[0] = fv[0], my_f[1] = fv[1], my_f[2] = fv[2];
+      }
+    }
+    const uint32_t flo = __builtin_amdgcn_alignbyte(my_f[1], my_f[0], r), fhi = __builtin_amdgcn_alignbyte(my_f[2], my_f[1], r);
+    // the field leaves the sums and counts as eight spaces
+    const uint32_t fsum = __builtin_amdgcn_sad_u8(fhi, 0u, __builtin_amdgcn_sad_u8(flo, 0u, 0u));
+    const uint32_t fneg = __popc(flo & 0x80808080u) + __popc(fhi & 0x80808080u);
+    const uint32_t all = my_acc & 0xFFFFFu;
+    const int64_t u = (int64_t)(all - fsum) + 8 * ' ';
+    const int64_t s = u - 256 * (int64_t)((my_acc >> 20) - fneg);
+    uint64_t want = 0;
+    const bool num = tar_chksum_field(flo, fhi, &want);
+    const bool live = lane < nb;
+    const unsigned long long hm = __ballot(live && num && ((int64_t)want == u || (int64_t)want == s));
+    const unsigned long long zm = __ballot(live && all == 0);
+    if (lane == 0) {
+      A.header[w] = hm;
+      A.zero[w] = zm;
+    }
+  }
+}
+
 // ---------------------------------------------------------------- K1
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // 8-byte aligned: one ds_read_b64
@@ -3981,12 +4120,15 @@ struct DeviceFetch {
   GatherSeg* gsegs = nullptr;  // the same for fetch_gather
   GatherSeg* gsegs_dev = nullptr;
   size_t gsegs_cap = 0;
+  uint64_t* marks = nullptr;  // device memory: mark_tar's two bitmaps, back to back
+  uint64_t marks_cap = 0;     // words
   ~DeviceFetch() {
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (st) (void)hipStreamSynchronize(st);
     if (segs) (void)hipHostFree(segs);
     if (gsegs) (void)hipHostFree(gsegs);
+    if (marks) (void)hipFree(marks);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
@@ -4092,6 +4234,34 @@ int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uin
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(f->ev[1], f->st));
   HIP_TRY(hipEventSynchronize(f->ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  return TSG_OK;
+}
+
+int mark_tar(DeviceFetch* f, const uint8_t* d_tar, uint64_t tar_len, uint64_t* marks, float* ms) {
+  *ms = 0;
+  const uint64_t nblocks = tar_len / 512, words = (nblocks + 63) / 64;
+  if (!words) return TSG_OK;
+  std::lock_guard<std::mutex> g(f->m);
+  HIP_TRY(hipSetDevice(f->d->device));
+  if (f->marks_cap < 2 * words) {
+    if (f->marks) HIP_TRY(hipFree(f->marks));
+    f->marks = nullptr;
+    f->marks_cap = 0;
+    const uint64_t cap = 2 * words + words / 2 + 1024;
+    HIP_TRY(hipMalloc((void**)&f->marks, sizeof(uint64_t) * cap));
+    f->marks_cap = cap;
+  }
+  TarMarkArgs A{d_tar, tar_len, f->marks, f->marks + words, nblocks, words};
+  // a wave per bitmap word, four per workgroup; past 8 workgroups per CU the grid strides
+  const int grid = (int)std::min<uint64_t>((words + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  tar_mark_kernel<<<grid, 256, 0, f->st>>>(A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  // both bitmaps in one D2H (they lie back to back)
+  HIP_TRY(hipMemcpyAsync(marks, f->marks, sizeof(uint64_t) * 2 * words, hipMemcpyDeviceToHost, f->st));
+  HIP_TRY(hipStreamSynchronize(f->st));
   HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
   return TSG_OK;
 }

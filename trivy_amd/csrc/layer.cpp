@@ -17,6 +17,7 @@
 #include <string>
 #include <string_view>
 #include <functional>
+#include <map>
 #include <memory>
 #include <vector>
 #include <thread>
@@ -312,13 +313,28 @@ bool zero_block(const uint8_t* tar, uint64_t p) {
   return true;
 }
 
+// What the walk reads of a tar: the 512 bytes of the header block at a position, and the
+// bytes of an extended header's payload.  MemTar is the archive in host memory; SparseTar
+// (below) answers from what was fetched of an archive in device memory.
+enum BlockKind { kHeaderBlock, kZeroBlock, kNeitherBlock };  // passes the checksum / all zero / neither
+struct MemTar {
+  const uint8_t* tar;
+  BlockKind kind(uint64_t pos, const uint8_t** h) const {
+    *h = tar + pos;
+    return zero_block(tar, pos) ? kZeroBlock : checksum_ok(tar + pos) ? kHeaderBlock : kNeitherBlock;
+  }
+  // (never null here; a null answer means "not fetched yet": the walk goes on by the header's size)
+  const uint8_t* payload(uint64_t dpos, uint64_t, char) const { return tar + dpos; }
+};
+
 // archive/tar Reader.Next from header position `pos`: appends entries while the position
 // of the next entry group (its first extended header, or its header) is < stop.  Returns
 // the position of the first group at or past stop (its headers unread), tar_len when the
 // archive ended, or (uint64_t)-1 with *err on a malformed archive.  `groups` (optional)
 // receives the position at which each appended entry's group starts.
-uint64_t walk_tar(const uint8_t* tar, uint64_t tar_len, uint64_t pos, uint64_t stop, std::vector<TarEntry>* out,
-                  std::vector<uint64_t>* groups, std::string* err) {
+template <class Tar>
+uint64_t walk_tar_on(const Tar& T, uint64_t tar_len, uint64_t pos, uint64_t stop, std::vector<TarEntry>* out,
+                     std::vector<uint64_t>* groups, std::string* err) {
   std::string long_name;
   bool have_long = false;
   std::vector<std::pair<std::string, std::string>> pax;
@@ -334,15 +350,17 @@ uint64_t walk_tar(const uint8_t* tar, uint64_t tar_len, uint64_t pos, uint64_t s
     }
     if (pos == tar_len) return have_long || !pax.empty() ? bad("unexpected EOF") : tar_len;
     if (tar_len - pos < 512) return bad("unexpected EOF");
-    const uint8_t* h = tar + pos;
-    if (zero_block(tar, pos)) {  // end: two zero blocks (or one, then end of input)
+    const uint8_t* h;
+    const BlockKind kd = T.kind(pos, &h);
+    if (kd == kZeroBlock) {  // end: two zero blocks (or one, then end of input)
       const uint64_t p2 = pos + 512;
       if (p2 == tar_len) return tar_len;
       if (tar_len - p2 < 512) return bad("unexpected EOF");
-      if (zero_block(tar, p2)) return tar_len;
+      const uint8_t* h2;
+      if (T.kind(p2, &h2) == kZeroBlock) return tar_len;
       return bad("invalid header");
     }
-    if (!checksum_ok(h)) return bad("invalid header");
+    if (kd != kHeaderBlock) return bad("invalid header");
     int64_t size;
     if (!parse_num(h + 124, 12, &size) || size < 0) return bad("invalid size");
     char type = (char)h[156];
@@ -356,11 +374,12 @@ uint64_t walk_tar(const uint8_t* tar, uint64_t tar_len, uint64_t pos, uint64_t s
     if (dpos > tar_len) return bad("unexpected EOF");
     if (type == 'x' || type == 'L' || type == 'K') {
       if ((uint64_t)size > tar_len - dpos) return bad("unexpected EOF");
+      const uint8_t* pl = T.payload(dpos, (uint64_t)size, type);
       if (type == 'x') {
-        if (!parse_pax(tar + dpos, (size_t)size, &pax)) return bad("invalid PAX record");
+        if (pl && !parse_pax(pl, (size_t)size, &pax)) return bad("invalid PAX record");
         if (pax.empty()) pax.emplace_back("", "");  // (an empty record set still binds)
       } else if (type == 'L') {
-        long_name = cstr(tar + dpos, (size_t)size);
+        if (pl) long_name = cstr(pl, (size_t)size);
         have_long = true;
       }
       pos = dpos + (((uint64_t)size + 511) & ~511ull);
@@ -388,6 +407,11 @@ uint64_t walk_tar(const uint8_t* tar, uint64_t tar_len, uint64_t pos, uint64_t s
     if (groups) groups->push_back(group);
     pos = dpos + ((dlen + 511) & ~511ull);  // > the header's position: the walk always advances
   }
+}
+
+uint64_t walk_tar(const uint8_t* tar, uint64_t tar_len, uint64_t pos, uint64_t stop, std::vector<TarEntry>* out,
+                  std::vector<uint64_t>* groups, std::string* err) {
+  return walk_tar_on(MemTar{tar}, tar_len, pos, stop, out, groups, err);
 }
 
 // The index of a whole tar stream.  The header chain is inherently sequential (each size
@@ -599,6 +623,11 @@ namespace tsg {
 // utils.IsBinary for the other ingest paths (internal.hpp: the emulated gate of pipeline.cpp)
 bool is_binary_head(const uint8_t* p, uint64_t n) { return is_binary(p, (int64_t)std::min<uint64_t>(n, 300)); }
 
+void tar_block_marks(const uint8_t* block, bool* header, bool* zero) {
+  *header = checksum_ok(block);
+  *zero = zero_block(block, 0);
+}
+
 struct SinkError {
   int rc;
   std::string msg;
@@ -757,13 +786,21 @@ namespace {
 // copied into the batch (the sink) in parallel
 // the gates of the walked files in parallel; the kept ones (in walk order) get their
 // offsets and "/"-prefixed paths in L; returns their indices into walked
-std::vector<size_t> gate_kept(const uint8_t* tar, const Gate& g, const std::vector<Walked>& walked, tsg_layer* L) {
+// keep[i]: Required(path, size), and with `tar` also not IsBinary (tar null: Required alone,
+// for a tar the host cannot read -- the binary gate then runs on the device)
+std::vector<uint8_t> gate_flags(const uint8_t* tar, const Gate& g, const std::vector<Walked>& walked) {
   const size_t n = walked.size();
   std::vector<uint8_t> keep(n);
   pool_for(n, 16, [&](size_t i) {
     const Walked& w = walked[i];
-    keep[i] = g.required(w.fp, (int64_t)w.size) && !is_binary(tar + w.dpos, (int64_t)w.size);
+    keep[i] = g.required(w.fp, (int64_t)w.size) && !(tar && is_binary(tar + w.dpos, (int64_t)w.size));
   }, 64);
+  return keep;
+}
+
+std::vector<size_t> gate_kept(const uint8_t* tar, const Gate& g, const std::vector<Walked>& walked, tsg_layer* L) {
+  const size_t n = walked.size();
+  const std::vector<uint8_t> keep = gate_flags(tar, g, walked);
   std::vector<size_t> kept;
   uint64_t total = 0;
   for (size_t i = 0; i < n; i++)
@@ -936,6 +973,263 @@ extern "C" int tsg_layer_scan(tsg_ctx* ctx, const uint8_t* tar, uint64_t tar_len
     if (rc) return rc;
     *layer = L.release();
     return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(TSG_ERR_NOMEM, "out of memory");
+  } catch (const std::exception& e) {
+    return fail(TSG_ERR_INTERNAL, e.what());
+  }
+}
+
+// ---------------------------------------------------------------- a layer tar in device memory
+namespace tsg {
+namespace {
+
+// The walk's view of a tar the host cannot read (tsg_device_layer_scan).  The device marked
+// every block that passes the header checksum and every all-zero block; the marked blocks
+// were fetched, in block order.  A position is then a header (its fetched block), a zero
+// block, or neither -- which is all walk_tar asks of a header position: the result is that
+// of the walk over the full bytes.  Extended-header payloads are served
+// once fetched; one asked for before that is noted in `missing`, and the walk goes on by the
+// header's own size (its result is then provisional: the caller fetches and walks again).
+struct SparseTar {
+  const uint64_t* header_bits = nullptr;
+  const uint64_t* zero_bits = nullptr;
+  const uint8_t* blocks = nullptr;   // the marked blocks, 512 bytes each
+  std::vector<uint64_t> rank;        // marked blocks before word w
+  struct Payload {
+    uint64_t size;
+    std::vector<uint8_t> bytes;
+  };
+  std::map<uint64_t, Payload> payloads;  // by data position
+  mutable std::vector<std::pair<uint64_t, uint64_t>> missing;  // {dpos, size}
+
+  void index(uint64_t words) {
+    rank.assign(words + 1, 0);
+    for (uint64_t w = 0; w < words; w++) rank[w + 1] = rank[w] + (uint64_t)__builtin_popcountll(header_bits[w]);
+  }
+  BlockKind kind(uint64_t pos, const uint8_t** h) const {
+    const uint64_t b = pos / 512, w = b / 64, bit = 1ull << (b % 64);
+    *h = nullptr;  // (read only of a header block)
+    if (header_bits[w] & bit) {
+      *h = blocks + 512 * (rank[w] + (uint64_t)__builtin_popcountll(header_bits[w] & (bit - 1)));
+      return kHeaderBlock;
+    }
+    return (zero_bits[w] & bit) ? kZeroBlock : kNeitherBlock;
+  }
+  const uint8_t* payload(uint64_t dpos, uint64_t size, char) const {
+    static const uint8_t kEmpty[1] = {};
+    if (!size) return kEmpty;
+    auto it = payloads.find(dpos);
+    if (it != payloads.end() && it->second.size == size) return it->second.bytes.data();
+    missing.emplace_back(dpos, size);
+    return nullptr;
+  }
+};
+
+// The chain followed by the headers' own sizes alone, no entry built: every extended header
+// met is asked for (noted in T.missing).  Stops without a verdict wherever walk_tar would
+// stop or fail; what it misses (a PAX size= that moves the chain) the exact walk asks for.
+void note_ext_headers(const SparseTar& T, uint64_t tar_len) {
+  uint64_t pos = 0;
+  while (tar_len - pos >= 512) {
+    const uint8_t* h;
+    if (T.kind(pos, &h) != kHeaderBlock) return;
+    int64_t size;
+    if (!parse_num(h + 124, 12, &size) || size < 0) return;
+    const char type = (char)h[156];
+    const uint64_t dpos = pos + 512;
+    uint64_t dlen = (uint64_t)size;
+    if (type == 'x' || type == 'L' || type == 'K') {
+      if (dlen > tar_len - dpos) return;
+      (void)T.payload(dpos, dlen, type);
+    } else {
+      size_t n = 0;
+      while (n < 100 && h[n]) n++;
+      const bool dir = type == 0 && (n ? h[n - 1] == '/' : std::memcmp(h + 257, "ustar\0" "00", 8) == 0 && h[345] != 0);
+      if (header_only(dir ? '5' : type)) dlen = 0;
+      if (dlen > tar_len - dpos) return;
+    }
+    pos = dpos + ((dlen + 511) & ~511ull);
+  }
+}
+
+struct PinLease {  // a pinned buffer of the context's pool for the length of a call
+  tsg_ctx* c;
+  PinBuf b;
+  explicit PinLease(tsg_ctx* ctx) : c(ctx) {}
+  ~PinLease() { ctx_pin_give(c, &b); }
+};
+
+int device_layer_scan(tsg_ctx* ctx, const void* d_tar, uint64_t tar_len, const Gate& g, tsg_layer** layer,
+                      tsg_result** out) {
+  // TSG_LAYER_PROF: wall time of the marks, the header gather, the walks with their payload
+  // rounds, classify + Required, the submits, and collecting
+  const bool prof = getenv("TSG_LAYER_PROF") != nullptr;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+  };
+  const auto p0 = now();
+  tsg_device_layer_stats st{};
+  st.tar_bytes = tar_len;
+  st.blocks = tar_len / 512;
+  const uint64_t words = (st.blocks + 63) / 64;
+  // 1. the marks: the one pass over every byte
+  std::vector<uint64_t> marks(2 * words + 1, 0);
+  int rc = ctx_tar_marks(ctx, d_tar, tar_len, marks.data(), &st.mark_ms);
+  if (rc) return rc;
+  const auto p1 = now();
+  SparseTar T;
+  T.header_bits = marks.data();
+  T.zero_bits = marks.data() + words;
+  T.index(words);
+  st.marked_blocks = T.rank[words];
+  st.header_bytes = 512 * st.marked_blocks;
+  // 2. every marked block into pinned memory (adjacent blocks merge into one range)
+  PinLease headers(ctx), scratch(ctx);
+  {
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;
+    for (uint64_t w = 0; w < words; w++)
+      for (uint64_t m = marks[w]; m; m &= m - 1) {
+        const uint64_t at = 512 * (w * 64 + (uint64_t)__builtin_ctzll(m));
+        if (!ranges.empty() && ranges.back().first + ranges.back().second == at) ranges.back().second += 512;
+        else ranges.emplace_back(at, 512);
+      }
+    if ((rc = ctx_fetch_ranges(ctx, d_tar, tar_len, ranges.data(), ranges.size(), &headers.b))) return rc;
+    T.blocks = headers.b.p;
+  }
+  // 3. the walk, again after each round of payloads, until it asked for nothing it lacked
+  const auto p2 = now();
+  std::vector<TarEntry> entries;
+  for (bool first = true;; first = false) {
+    entries.clear();
+    T.missing.clear();
+    std::string err;
+    uint64_t end = 0;
+    if (first) note_ext_headers(T, tar_len);  // by the header sizes alone
+    else end = walk_tar_on(T, tar_len, 0, tar_len, &entries, nullptr, &err);
+    if (T.missing.empty()) {
+      if (first) continue;
+      if (end == ~0ull) return fail(TSG_ERR_ARG, std::string("failed to extract the archive: ") + err);
+      break;
+    }
+    // (walk_tar has checked each against the tar's end before asking for it)
+    std::sort(T.missing.begin(), T.missing.end());
+    T.missing.erase(std::unique(T.missing.begin(), T.missing.end()), T.missing.end());
+    if ((rc = ctx_fetch_ranges(ctx, d_tar, tar_len, T.missing.data(), T.missing.size(), &scratch.b))) return rc;
+    uint64_t at = 0;
+    for (const auto& m : T.missing) {
+      SparseTar::Payload& p = T.payloads[m.first];
+      p.size = m.second;
+      p.bytes.assign(scratch.b.p + at, scratch.b.p + at + m.second);
+      at += m.second;
+      st.payloads++;
+      st.payload_bytes += m.second;
+    }
+    st.payload_rounds++;
+  }
+  st.chain_entries = entries.size();
+  const auto p3 = now();
+  // 4. the walker's logic and Required on the host, as tsg_layer_scan
+  auto L = std::make_unique<tsg_layer>();
+  std::vector<std::string> skipped;
+  std::vector<Walked> walked;
+  classify(entries, 0, g, &skipped, L.get(), &walked);
+  const std::vector<uint8_t> req = gate_flags(nullptr, g, walked);
+  std::vector<size_t> cand;  // Required files, in walk order
+  uint64_t total = 0;
+  for (size_t i = 0; i < walked.size(); i++)
+    if (req[i]) {
+      cand.push_back(i);
+      total += walked[i].size;
+    }
+  const auto p4 = now();
+  // 5. spans batches cut like scan_in_pieces' pieces, all submitted before the first is collected
+  const uint64_t floor_mib = knobs().piece_mib.load() > 0 ? (uint64_t)knobs().piece_mib.load() : 16;
+  const uint64_t piece_bytes = std::min(ctx_slot_bytes(ctx), std::max<uint64_t>(floor_mib << 20, total / 8));
+  struct Piece {
+    size_t a, b;  // cand[a, b)
+    uint64_t ticket;
+    std::vector<uint8_t> kept;
+  };
+  std::vector<Piece> pieces;
+  size_t i = 0;
+  while (i < cand.size() && rc == TSG_OK) {
+    const size_t a = i;
+    uint64_t bytes = 0;
+    while (i < cand.size() && (i == a || bytes + walked[cand[i]].size <= piece_bytes)) bytes += walked[cand[i++]].size;
+    std::vector<uint64_t> starts, lengths, poffs{0};
+    std::string paths;
+    for (size_t k = a; k < i; k++) {
+      const Walked& w = walked[cand[k]];
+      starts.push_back(w.dpos);
+      lengths.push_back(w.size);
+      paths += '/';
+      paths += w.fp;
+      poffs.push_back(paths.size());
+    }
+    Piece p{a, i, 0, std::vector<uint8_t>(i - a, 0)};
+    rc = tsg_device_spans_submit(ctx, d_tar, tar_len, starts.data(), lengths.data(), (uint32_t)(i - a), paths.data(),
+                                 poffs.data(), TSG_SPANS_BINARY_GATE, p.kept.data(), &p.ticket);
+    if (!rc) pieces.push_back(std::move(p));
+  }
+  std::string first_err = rc ? tsg_last_error() : "";
+  const auto p5 = now();
+  // every submitted batch is collected, also after a failure (nothing stays pending)
+  auto res = std::make_unique<tsg_result>();
+  res->buf.assign(8, '\0');
+  for (const Piece& p : pieces) {
+    tsg_result* r = nullptr;
+    uint64_t fetched = 0;
+    const int e = ctx_collect_device(ctx, p.ticket, &r, &fetched);
+    if (e) {
+      if (!rc) {
+        rc = e;
+        first_err = tsg_last_error();
+      }
+      continue;
+    }
+    st.fetched_bytes += fetched;
+    res->buf.append(r->buf, 8, std::string::npos);  // the batch's records (after its header)
+    tsg_result_free(r);
+    for (size_t k = p.a; k < p.b; k++) {
+      if (!p.kept[k - p.a]) continue;  // binary: left out of the layer and the result
+      const Walked& w = walked[cand[k]];
+      L->offsets.push_back(L->offsets.back() + w.size);
+      L->paths += '/';
+      L->paths += w.fp;
+      L->path_offsets.push_back(L->paths.size());
+    }
+  }
+  if (rc) return fail(rc, first_err);
+  if (prof)
+    fprintf(stderr, "device layer: marks %.1f ms (kernel %.2f), header gather %.1f ms, walk + %llu payload round(s) %.1f ms, "
+            "classify + Required %.1f ms, %zu submits %.1f ms, collect %.1f ms\n", ms(p0, p1), st.mark_ms, ms(p1, p2),
+            (unsigned long long)st.payload_rounds, ms(p2, p3), ms(p3, p4), pieces.size(), ms(p4, p5), ms(p5, now()));
+  const uint32_t hdr[2] = {0x31475354u, (uint32_t)(L->offsets.size() - 1)};
+  std::memcpy(&res->buf[0], hdr, 8);
+  st.span_batches = pieces.size();
+  st.files_scanned = L->offsets.size() - 1;
+  st.pcie_bytes = st.header_bytes + st.payload_bytes + st.fetched_bytes;
+  ctx_device_layer_done(ctx, st);
+  *layer = L.release();
+  *out = res.release();
+  return TSG_OK;
+}
+
+}  // namespace
+}  // namespace tsg
+
+extern "C" int tsg_device_layer_scan(tsg_ctx* ctx, const void* d_tar, uint64_t tar_len,
+                                     const char* const* skip_files, uint32_t n_skip_files,
+                                     const char* const* skip_dirs, uint32_t n_skip_dirs, const char* config_path,
+                                     tsg_layer** layer, tsg_result** out) {
+  if (!ctx || !layer || !out || (!d_tar && tar_len)) return fail(TSG_ERR_ARG, "bad argument");
+  *layer = nullptr;
+  *out = nullptr;
+  try {
+    const Gate g = make_gate(ctx_ruleset(ctx), skip_files, n_skip_files, skip_dirs, n_skip_dirs, config_path);
+    return device_layer_scan(ctx, d_tar, tar_len, g, layer, out);
   } catch (const std::bad_alloc&) {
     return fail(TSG_ERR_NOMEM, "out of memory");
   } catch (const std::exception& e) {

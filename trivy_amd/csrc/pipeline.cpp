@@ -165,6 +165,8 @@ struct tsg_ctx {
   DeviceFetch* fetch = nullptr;
   tsg_device_input_stats dstats{};
   tsg_device_spans_stats sstats{};
+  tsg_device_layer_stats lstats{};
+  std::vector<PinBuf> pin_pool;  // idle buffers of ctx_fetch_ranges (tsg_device_layer_scan)
   int mirror_slot = -1;
   uint64_t mirror_take = 0;  // Slot::takes when the batch had it: a later taker overwrites the mirror
   uint64_t mirror_bytes = 0;
@@ -180,6 +182,10 @@ struct tsg_ctx {
     for (auto& t : workers) t.join();
     if (!emulate) (void)hipSetDevice(device);
     if (fetch) fetch_destroy(fetch);
+    for (auto& b : pin_pool) {
+      if (emulate) free(b.p);
+      else (void)hipHostFree(b.p);
+    }
     for (auto* l : lanes) lane_destroy(l);
     for (auto& o : outs) host_out_free(&o);
     for (auto& s : slots) {
@@ -1188,6 +1194,156 @@ int tsg_ctx_get_device_spans_stats(const tsg_ctx* c, tsg_device_spans_stats* out
   std::lock_guard<std::mutex> g(c->m);
   *out = c->sstats;
   return TSG_OK;
+}
+
+}  // extern "C"
+
+// ---- a layer tar in device memory: the device side of layer.cpp's tsg_device_layer_scan
+namespace tsg {
+
+int ctx_tar_marks(tsg_ctx* c, const void* d_tar, uint64_t tar_len, uint64_t* marks, double* ms) {
+  *ms = 0;
+  const uint64_t nblocks = tar_len / 512, words = (nblocks + 63) / 64;
+  if (c->emulate) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* tar = (const uint8_t*)d_tar;
+    pool_for((size_t)words, c->nt, [&](size_t w) {
+      uint64_t h = 0, z = 0;
+      for (uint64_t b = 64 * (uint64_t)w; b < std::min<uint64_t>(nblocks, 64 * (uint64_t)w + 64); b++) {
+        bool hdr, zero;
+        tar_block_marks(tar + 512 * b, &hdr, &zero);
+        h |= (uint64_t)hdr << (b % 64);
+        z |= (uint64_t)zero << (b % 64);
+      }
+      marks[w] = h;
+      marks[words + w] = z;
+    }, 64);
+    *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return TSG_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  float fms = 0;
+  const int rc = mark_tar(c->fetch, (const uint8_t*)d_tar, tar_len, marks, &fms);
+  *ms = fms;
+  return rc;
+}
+
+void ctx_pin_give(tsg_ctx* c, PinBuf* b) {
+  if (!b->p) return;
+  std::lock_guard<std::mutex> g(c->m);
+  c->pin_pool.push_back(*b);
+  *b = PinBuf{};
+}
+
+int ctx_fetch_ranges(tsg_ctx* c, const void* d_base, uint64_t base_bytes, const std::pair<uint64_t, uint64_t>* ranges,
+                     size_t n, PinBuf* dst) {
+  GatherList gl;
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (ranges[i].first > base_bytes || ranges[i].second > base_bytes - ranges[i].first)
+      return fail(TSG_ERR_INTERNAL, "fetch range outside the buffer");
+    gl.add(ranges[i].first, total, ranges[i].second);
+    total += ranges[i].second;
+  }
+  gl.flush();
+  if (!total) return TSG_OK;
+  if (!c->emulate) HIP_TRY(hipSetDevice(c->device));
+  if (dst->cap < total) {  // an idle buffer that is large enough, else a new one in a smaller one's place
+    PinBuf old = *dst;
+    *dst = PinBuf{};
+    {
+      std::lock_guard<std::mutex> g(c->m);
+      for (size_t k = 0; k < c->pin_pool.size() && !dst->p; k++)
+        if (c->pin_pool[k].cap >= total) {
+          *dst = c->pin_pool[k];
+          c->pin_pool.erase(c->pin_pool.begin() + (long)k);
+        }
+      if (!dst->p && !old.p && !c->pin_pool.empty()) {
+        old = c->pin_pool.back();
+        c->pin_pool.pop_back();
+      }
+    }
+    host_free(!c->emulate, old.p);
+    if (!dst->p) {
+      const uint64_t cap = round_up(total + total / 4, 1 << 16);
+      void* p = nullptr;
+      if (c->emulate) p = malloc(cap);
+      else HIP_TRY(hipHostMalloc(&p, cap, hipHostMallocMapped));
+      if (!p) return fail(TSG_ERR_NOMEM, "cannot allocate a pinned buffer");
+      dst->p = (uint8_t*)p;
+      dst->cap = cap;
+    }
+  }
+  if (c->emulate) {
+    for (const GatherSeg& s : gl.segs) std::memcpy(dst->p + s.dst, (const uint8_t*)d_base + s.src, s.len);
+    return TSG_OK;
+  }
+  float ms = 0;
+  return fetch_gather(c->fetch, (const uint8_t*)d_base, base_bytes, dst->p, total, gl.segs.data(), gl.segs.size(), &ms);
+}
+
+int ctx_collect_device(tsg_ctx* c, uint64_t ticket, tsg_result** out, uint64_t* fetched_bytes) {
+  std::shared_ptr<Batch> b;
+  {
+    std::lock_guard<std::mutex> g(c->m);
+    auto it = c->pending.find(ticket);
+    if (it == c->pending.end()) return fail(TSG_ERR_ARG, "no such submitted batch (unknown or already collected ticket)");
+    b = it->second;
+    c->pending.erase(it);
+  }
+  if (int rc = finish(b)) return rc;
+  *fetched_bytes = b->fetched_bytes;
+  *out = b->res.release();
+  return TSG_OK;
+}
+
+void ctx_device_layer_done(tsg_ctx* c, const tsg_device_layer_stats& last) {
+  std::lock_guard<std::mutex> g(c->m);
+  tsg_device_layer_stats& s = c->lstats;
+  tsg_device_layer_stats n = last;
+  n.calls = s.calls + 1;
+  n.sum_tar_bytes = s.sum_tar_bytes + last.tar_bytes;
+  n.sum_blocks = s.sum_blocks + last.blocks;
+  n.sum_marked_blocks = s.sum_marked_blocks + last.marked_blocks;
+  n.sum_chain_entries = s.sum_chain_entries + last.chain_entries;
+  n.sum_header_bytes = s.sum_header_bytes + last.header_bytes;
+  n.sum_payloads = s.sum_payloads + last.payloads;
+  n.sum_payload_bytes = s.sum_payload_bytes + last.payload_bytes;
+  n.sum_payload_rounds = s.sum_payload_rounds + last.payload_rounds;
+  n.sum_span_batches = s.sum_span_batches + last.span_batches;
+  n.sum_files_scanned = s.sum_files_scanned + last.files_scanned;
+  n.sum_fetched_bytes = s.sum_fetched_bytes + last.fetched_bytes;
+  n.sum_pcie_bytes = s.sum_pcie_bytes + last.pcie_bytes;
+  n.sum_mark_ms = s.sum_mark_ms + last.mark_ms;
+  s = n;
+}
+
+}  // namespace tsg
+
+extern "C" {
+
+int tsg_ctx_get_device_layer_stats(const tsg_ctx* c, tsg_device_layer_stats* out) {
+  if (!c || !out) return fail(TSG_ERR_ARG, "bad argument");
+  std::lock_guard<std::mutex> g(c->m);
+  *out = c->lstats;
+  return TSG_OK;
+}
+
+int tsg_test_device_tar_marks(tsg_ctx* c, const void* d_tar, uint64_t tar_len, uint64_t* header_bits,
+                              uint64_t* zero_bits, uint64_t words_cap) {
+  const uint64_t words = (tar_len / 512 + 63) / 64;
+  if (!c || (!d_tar && tar_len) || words > words_cap || (words && (!header_bits || !zero_bits)))
+    return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    std::vector<uint64_t> marks(2 * words + 1, 0);
+    double ms = 0;
+    if (int rc = ctx_tar_marks(c, d_tar, tar_len, marks.data(), &ms)) return rc;
+    if (words) {
+      std::memcpy(header_bits, marks.data(), sizeof(uint64_t) * words);
+      std::memcpy(zero_bits, marks.data() + words, sizeof(uint64_t) * words);
+    }
+    return TSG_OK;
+  });
 }
 
 int tsg_device_submit(tsg_ctx* c, const void* d_data, const uint64_t* offsets, uint32_t nfiles, const char* paths,

@@ -797,6 +797,32 @@ class GpuContext:
         N.check(N.lib().tsg_ctx_get_device_spans_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in N.DeviceSpansStats._fields_}
 
+    def device_layer_stats(self):
+        """tsg_device_layer_stats of the context's scan_layer_tensor calls."""
+        s = N.DeviceLayerStats()
+        N.check(N.lib().tsg_ctx_get_device_layer_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in N.DeviceLayerStats._fields_}
+
+    def tar_marks(self, data):
+        """Test hook (tsg_test_device_tar_marks): what tar_mark_kernel, or its emulation,
+        says of every whole 512-byte block of the tensor `data` (as scan_layer_tensor takes
+        it): (header, zero), two bool arrays of data.numel() // 512 entries."""
+        self._check_tensor(data)
+        self._sync_tensor(data)
+        n = data.numel()
+        nblocks = n // 512
+        words = (nblocks + 63) // 64
+        hdr = np.zeros(words + 1, dtype=np.uint64)
+        zero = np.zeros(words + 1, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        N.check(N.lib().tsg_test_device_tar_marks(self._h, C.c_void_p(data.data_ptr() if n else None), C.c_uint64(n),
+                                                  hdr.ctypes.data_as(u64p), zero.ctypes.data_as(u64p),
+                                                  C.c_uint64(words)))
+
+        def bits(a):
+            return np.unpackbits(a[:words].view(np.uint8), bitorder="little")[:nblocks].astype(bool)
+        return bits(hdr), bits(zero)
+
     def stats(self):
         s = N.Stats()
         N.check(N.lib().tsg_ctx_get_stats(self._h, C.byref(s)))

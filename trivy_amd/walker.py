@@ -506,6 +506,25 @@ def scan_layer_pipelined(ctx, tar, skip_files=(), skip_dirs=(), config_path=""):
     return _pipelined_result(ctx, h, out)
 
 
+def scan_layer_tensor(ctx, data, skip_files=(), skip_dirs=(), config_path=""):
+    """tsg_device_layer_scan: scan_layer_pipelined for an uncompressed layer tar that lies in
+    GPU memory: `data` is a torch.uint8 tensor on the context's device (a host tensor for an
+    emulated context; the checks are GpuContext.scan_spans').  The tar is indexed on the
+    device, the header chain is walked on the host over the fetched header blocks, and the
+    files are scanned where they lie.  Returns (paths, results, opq, wh, walked), equal to
+    scan_layer_pipelined's for the same bytes."""
+    ctx._check_tensor(data)
+    ctx._sync_tensor(data)
+    n = data.numel()
+    h, out = C.c_void_p(), C.c_void_p()
+    N.check(N.lib().tsg_device_layer_scan(ctx.handle, C.c_void_p(data.data_ptr() if n else None), n,
+                                          _cstrs(list(skip_files)), len(skip_files),
+                                          _cstrs(list(skip_dirs)), len(skip_dirs),
+                                          config_path.encode("utf-8", "surrogateescape"),
+                                          C.byref(h), C.byref(out)))
+    return _pipelined_result(ctx, h, out)
+
+
 def scan_fs_pipelined(ctx, root, skip_files=(), skip_dirs=(), config_path=""):
     """tsg_fs_scan: walk, gate and scan a tree in one pipelined call."""
     h, out = C.c_void_p(), C.c_void_p()
@@ -548,3 +567,10 @@ def analyze_layer_native(analyzer, tar, device=None, ctx=None, emulate_chunk=0,
     res = analyzer.scanner.ScanBatch(lay.batch, device=device, ctx=ctx,
                                      emulate_chunk=emulate_chunk) if lay.batch.nfiles else []
     return sort_secrets([r for r in res if r["Findings"]]), lay.opq, lay.wh
+
+
+def analyze_layer_tensor(analyzer, data, ctx, skip_files=(), skip_dirs=()):
+    """analyze_layer_native for a layer tar in GPU memory (scan_layer_tensor): the sorted
+    AnalysisResult.Secrets, the opaque dirs and the whiteouts."""
+    _, res, opq, wh, _ = scan_layer_tensor(ctx, data, skip_files, skip_dirs, analyzer.configPath)
+    return sort_secrets([r for r in res if r["Findings"]]), opq, wh
