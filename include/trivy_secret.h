@@ -242,6 +242,19 @@ int tsg_batch_kernels(tsg_ctx* ctx, uint32_t slot_id, uint32_t nfiles, uint32_t*
 int tsg_batch_items(tsg_ctx* ctx, uint32_t slot_id, uint32_t* entries, size_t entries_cap,
                     uint32_t* dentries, size_t dentries_cap, uint32_t* items, size_t items_cap,
                     uint8_t* gskip, size_t gskip_len, uint64_t* n);
+/* Test hook: what K2 and the outputs kernel of the last tsg_batch_kernels handed to the host,
+ * read from the batch's pinned output block (same contract as tsg_batch_items: same slot,
+ * nothing submitted in between, not on an emulated context: TSG_ERR_ARG otherwise).
+ * n[0..3] = candidate records K2 reserved (tsg_stats.candidates), records in the block
+ * (min(n[0], candidate capacity)), files of the batch, the candidate capacity; up to the
+ * given capacities are copied (any pointer may be NULL):
+ *   records  3 u32 each {file, rule, end}, as written, in the device's order (the forms:
+ *            tsg_emulate_candidates)
+ *   flags    [files] 1 = overflow (resolve the file whole), 2 = folding runes present,
+ *            4 = the file's keyword row was written
+ *   kw       [files * kw_words] the keyword rows of the files with flag 4, zero elsewhere */
+int tsg_batch_candidates(tsg_ctx* ctx, uint32_t slot_id, uint32_t* records, size_t records_cap,
+                         uint8_t* flags, size_t flags_len, uint32_t* kw, size_t kw_len, uint64_t* n);
 
 typedef struct tsg_stats {
   double k1_ms;          /* K1 literal automaton + run counters, last collected batch (HIP events) */
@@ -500,6 +513,41 @@ int tsg_emulate_candidate_stats(const tsg_ruleset* rs, const uint8_t* data,
 int tsg_emulate_items(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
                       uint32_t nfiles, uint32_t chunk, uint32_t max_back, uint32_t* triples,
                       size_t triples_cap, uint64_t* counts, uint64_t* n_items);
+
+/* What K2 writes for one batch, record by record and in the device's own form (plan.hpp
+ * emulate_candidates): the reference of tsg_batch_candidates.  chunk and ext_cap are the
+ * context's chunk_bytes and ext_cap (the value in use, not 0), items_cap and max_dense the
+ * layout's (tsg_layout_reference), word_recs = 0 the form of the k2_no_word_recs knob.  A
+ * record is 3 u32 {file, rule, end}: rule < 2^31 is a rule index and end the match's end
+ * offset in the file, the file's length for an accept at end of text, or 0xFFFFFFFF
+ * ("resolve this rule over the whole file"); rule with bit 31 is a transition record {group
+ * = bits 16-30, table index = bits 0-15} of the accepting transition at `end`; with bit 30
+ * too (groups then have 14 bits) a word record: the row before the byte at `end`, whose
+ * 16-byte word of the batch accepts.  No candidate capacity is applied.  records (or NULL):
+ * up to records_cap records in reference order; *n_records (or NULL): all of them. */
+int tsg_emulate_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
+                           uint32_t nfiles, uint32_t chunk, uint32_t ext_cap, uint64_t items_cap,
+                           uint32_t max_dense, uint32_t word_recs, uint32_t* records,
+                           size_t records_cap, uint64_t* n_records);
+
+/* The candidates of the emulation's own per-item form (plan.hpp emulate_kernels: run_segment
+ * over every item of emulate_items(max_back = 16), a tail behind each, no layout and no
+ * capacity), as (file, rule index, end) triples of 3 u32 in item order: the independent
+ * restatement that tsg_emulate_candidates' unique triples must equal where no group is dense
+ * and no tail reaches ext_cap.  triples (or NULL): up to triples_cap triples; *n_triples (or
+ * NULL): all of them. */
+int tsg_emulate_item_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
+                                uint32_t nfiles, uint32_t chunk, uint32_t ext_cap, uint32_t* triples,
+                                size_t triples_cap, uint64_t* n_triples);
+
+/* K2 records -> candidates, as the host resolver expands them (plan.hpp expand_candidate):
+ * triples of 3 u32 (file, rule index, end) in record order, 0xFFFFFFFF ends kept; a
+ * transition record gives one triple per rule of its accept mask, a word record those of
+ * every accepting transition from its byte to the end of its word (or file).  triples (or
+ * NULL): up to triples_cap triples; *n_triples (or NULL): all of them. */
+int tsg_expand_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
+                          uint32_t nfiles, const uint32_t* records, size_t n_records,
+                          uint32_t* triples, size_t triples_cap, uint64_t* n_triples);
 
 /* The device's item layout restated on the host (plan.hpp layout_reference), groups in id
  * order: kind[g] = 0 no items, 1 list, 2 dense, 3 skipped.  A group with counts[g] * 2 >

@@ -277,7 +277,7 @@ def reference_work_lists(tri, counts, nchunks, items_cap, max_dense=16):
             items, (kind == S.GROUP_SKIP).astype(np.uint8))
 
 
-def dense_batch(chunk, total):
+def dense_batch(chunk, total, long_tokens=False):
     """`total` bytes in which aws-access-key-id's group (gated by the keyword AKIA, no anchor:
     it listens to every chunk) and the first run-U group (keyword `key`, lines of long
     tokens) both have items in more than half of the chunks, so both want K2's dense pass.
@@ -286,7 +286,11 @@ def dense_batch(chunk, total):
     inside a lane's range and one exactly on it.  True aws-access-key-id matches straddle a
     lane range and every entry boundary, end a gated file that an ungated one follows, and
     end the batch.  The short files carry anchors of five finite-back groups (list groups
-    beside the dense ones).  Returns (batch, planted matches)."""
+    beside the dense ones).  With long_tokens, two tokens of 135 bytes keep the run-U group's
+    tails alive for more than 64 bytes: one over a chunk boundary inside the first file, whose
+    lane ranges all lie in that one file (Lane::streams), one over the end of the lane range in
+    which the second gated file starts (Lane::piece; it stands in that file's range-straddling
+    secret).  Returns (batch, planted matches)."""
     import numpy as np
     from trivy_amd import secret as S
     rng = np.random.default_rng(chunk)
@@ -314,6 +318,9 @@ def dense_batch(chunk, total):
         f = max(k for k in range(len(gated)) if cuts[k] <= b)
         assert gated[f] and cuts[f] + 32 < b < cuts[f + 1] - 32 or b + 1 == total, (b, cuts[f], cuts[f + 1])
     plants = []
+    long_token = b"key=" + b"Zz9" * 45 + b"\n"
+    # (a gated file that starts at least 24 bytes before the end of its first lane range)
+    piece_file = [f for f in range(len(gated)) if gated[f] and 0 < cuts[f] % R <= R - 24][0] if long_tokens else -1
 
     def plant(end):  # the secret's last byte at end - 1; a newline behind it, or the file's end
         data[end - len(AKIA) - 1:end] = b"\n" + AKIA
@@ -329,8 +336,14 @@ def dense_batch(chunk, total):
                 data[a + 2:a + 2 + len(lit)] = lit
             continue
         first = (a + R - 1) // R * R + R
-        if first + 40 < b:
+        if f == piece_file:              # the token runs 115 bytes past the range's end
+            assert first + 120 < b - 32
+            data[first - R - 20:first - R - 20 + len(long_token)] = long_token
+        elif first + 40 < b:
             plant(first + 7)             # straddles a lane range boundary
+        if long_tokens and f == 0:       # ... and past a chunk's end in the fourth range of file 0
+            assert a == 0 and b % R == 0 and 3 * R + chunk + 120 < b - 32
+            data[3 * R + chunk - 20:3 * R + chunk - 20 + len(long_token)] = long_token
         if f + 1 < len(gated):
             plant(b)                     # ends the file; an ungated file follows
     for b in range(E, total, E):
@@ -339,3 +352,386 @@ def dense_batch(chunk, total):
     plant(total)                         # ends at the batch's last byte
     args = [S.ScanArgs("d/%d.txt" % f, bytes(data[cuts[f]:cuts[f + 1]])) for f in range(len(gated))]
     return S.Batch.from_args(args), sorted(set(plants))
+
+
+# ---------------------------------------------------------------------------------------
+# K2's candidate records, record by record (tests/test_gpu_k2_records.py): the checker of the
+# device's records against Scanner.emulate_candidates, and inputs built for the edges of the
+# K2 kernels.  tests/test_k2_paths.py checks on the CPU that each input covers its edges.
+
+# A small rule set for what the builtin rules cannot give: a match shorter than a word with
+# several ends, an end-of-text assertion, a \b decided by the byte before the match, a
+# bounded tail longer than a chunk and an unbounded (?s).* tail (an immortal state).  The
+# literals have three bytes and more (anchors: finite-back list groups) and no letter of
+# the filler (fill()).  They are added to the builtin rules, none of which has a keyword in
+# these inputs: the rule set keeps the builtin groups' large tables, and with them the list
+# kernel the builtin rules run.
+K2_RULES_DOC = {"rules": [
+    {"id": "short", "category": "t", "title": "short", "severity": "LOW",
+     "regex": r"shk[0-9]{3,6}", "keywords": ["shk"]},
+    {"id": "eot", "category": "t", "title": "eot", "severity": "LOW",
+     "regex": r"eok[a-f]{3,8}$", "keywords": ["eok"]},
+    {"id": "wb", "category": "t", "title": "wb", "severity": "LOW",
+     "regex": r"\bwbk[0-9]{4}", "keywords": ["wbk"]},
+    {"id": "bounded", "category": "t", "title": "bounded", "severity": "LOW",
+     "regex": r"bdk=[a-z]{0,300};", "keywords": ["bdk="]},
+    {"id": "unb", "category": "t", "title": "unb", "severity": "LOW",
+     "regex": r"(?s)ubk\{.*\}", "keywords": ["ubk{"]},
+]}
+K2_CUSTOM_RULES = ("short", "eot", "wb", "bounded", "unb")
+WHOLE = 0xFFFFFFFF
+K2_CHUNKS = (128, 256, 48)   # k2_list_pair's word loop twice, Lane::piece once
+
+
+def k2_scanner():
+    """The scanner of K2_RULES_DOC; every rule must have a GPU program."""
+    from trivy_amd import secret as S
+    sc = S.NewScanner(S.config_from_dict(K2_RULES_DOC))
+    assert sc.info()["n_hostonly"] == 0 and all(sc.rule_group(r) >= 0 for r in range(len(sc.Rules)))
+    return sc
+
+
+def hostonly_scanner():
+    """The custom rules beside one rule no DFA fits (200 12-letter words in one alternation):
+    the host resolves it over every file, so outputs_kernel hands back every keyword row."""
+    import numpy as np
+    from trivy_amd import secret as S
+    rng = np.random.default_rng(7)
+    words = ["".join(rng.choice(list("abcdefghijklmnopqrstuvwxyz"), size=12)) for _ in range(200)]
+    doc = {"enable-builtin-rules": [AKIA_GROUP_RULE], "rules": K2_RULES_DOC["rules"] + [
+        {"id": "many-words", "category": "t", "title": "many words", "severity": "LOW",
+         "regex": "(?P<secret>(?:" + "|".join(words) + "))"}]}
+    sc = S.NewScanner(S.config_from_dict(doc))
+    assert sc.info()["n_hostonly"] == 1
+    return sc
+
+
+def with_group_mates(sc, want):
+    """The inputs' `want` lists name, for a tail past the cut, the rule whose tail it is: K2
+    hands the host every rule of that rule's group (kCandWhole).  Returns the sorted triples
+    with those group mates added."""
+    ids = [r.ID for r in sc.Rules]
+    group = [sc.rule_group(r) for r in range(len(ids))]
+    out = []
+    for f, rid, e in want:
+        mates = [ids[r] for r in range(len(ids)) if group[r] == group[ids.index(rid)]] if e == WHOLE else [rid]
+        out += [(f, m, e) for m in mates]
+    return sorted(out)
+
+
+def rule_index(sc, rule_id):
+    return [r.ID for r in sc.Rules].index(rule_id)
+
+
+def fill(n):
+    """n filler bytes: no keyword, no anchor literal, the last byte a letter."""
+    out = bytearray((b"qzx vjw qq\nzzv " * (n // 15 + 1))[:n])
+    if n:
+        out[-1] = ord("q")
+    return bytes(out)
+
+
+class _Files:
+    """Files laid out at chosen batch offsets: pad_to() puts a filler file in between."""
+
+    def __init__(self):
+        self.files, self.at = [], 0
+
+    def pad_to(self, off):
+        assert off >= self.at, (off, self.at)
+        if off > self.at:
+            self.add(fill(off - self.at))
+
+    def add(self, content):
+        self.files.append(bytes(content))
+        self.at += len(content)
+        return len(self.files) - 1
+
+    def batch(self):
+        from trivy_amd import secret as S
+        return S.Batch.from_args([S.ScanArgs("k/%d.txt" % i, c) for i, c in enumerate(self.files)])
+
+
+def _blob(n, plants):
+    """n filler bytes with the given {offset: bytes} written over them."""
+    out = bytearray(fill(n))
+    for at, b in plants.items():
+        assert 0 <= at and at + len(b) <= n, (at, len(b), n)
+        out[at:at + len(b)] = b
+    return bytes(out)
+
+
+def word_mask_batch(chunk):
+    """The list path's word masks and chain starts.  Returns (batch, want, notes): `want` is
+    the complete set of (file, rule id, end) triples of the custom rules, `notes` names the
+    files and offsets that test_k2_paths checks the edges on.
+      first: the batch's first file starts chunk 0 (base == 0, the file at the chunk's first
+        byte) with a `short` secret.
+      starts: for r in 1, 8, 15 a file that starts at in-chunk offset 32 + r behind a filler
+        file ending in a letter, with a `wb` secret at its first byte (stepping the byte
+        before the file would lose the \\b) -- its accept lies in the file's first, partial
+        word for r = 1 and 8; for r = 15 that word is one byte, the secret's first.
+      ends: for r in 1, 8, 15 a file that ends at offset r of a word with `short`'s accept on
+        its last byte, the next file continuing the digits in the same word.
+      splits: a `bounded` secret cut by a file boundary inside a word, on a word boundary
+        inside a chunk, and behind a chunk boundary (the tail stops at fe): no record.
+      body / tail: accepts at all 16 positions of a word, inside the secret's own chunk
+        (`short`) and in the chunk after it (`bounded`, from the chunk's last four bytes).
+      ctx: in one file, `wb` secrets at a chunk's first byte behind a letter (no match), a
+        space and a newline (matches): the three start contexts of an item that starts
+        mid-file.
+      last: a `short` secret in the batch's last, partial chunk."""
+    C = chunk
+    L = _Files()
+    want, notes = [], {}
+    f = L.add(_blob(20, {0: b"shk123 "}))
+    want += [(f, "short", 6)]
+    notes["first"] = f
+    notes["starts"], notes["ends"], notes["splits"] = {}, {}, {}
+    k = 2
+    for r in (1, 8, 15):
+        L.pad_to(k * C + 32 + r)
+        f = L.add(_blob(24, {0: b"wbk1234 "}))
+        want += [(f, "wb", 7)]
+        notes["starts"][r] = f
+        k += 2
+    for r in (1, 8, 15):
+        L.pad_to(k * C)
+        n = 16 + r
+        f = L.add(_blob(n, {n - 7: b"shk1234"}))      # ends "shk123" on its last byte, "shk1234" at fe
+        want += [(f, "short", n - 1), (f, "short", n)]
+        g = L.add(_blob(40, {0: b"56 ", 20: b"shk "}))  # gated (the keyword), no secret
+        notes["ends"][r] = (f, g)
+        k += 2
+    for name, cut in (("word", 16 * 2 + 5), ("boundary", 16 * 2), ("chunk", C + 5)):
+        L.pad_to(k * C)
+        secret = b"bdk=abcdefghijklmnopqrst;"
+        start = cut - 12                              # 12 bytes of the secret before the cut
+        if name == "chunk":
+            assert start < C < cut
+        both = _blob(cut + 60, {start: secret, cut + 30: b"bdk= "})
+        f = L.add(both[:cut])
+        g = L.add(both[cut:])
+        notes["splits"][name] = (f, g, cut)
+        k += 3
+    # accept ends at every position of a word: chunk j of one file (body), and behind the
+    # end of chunk 2j + 1 of another (tail)
+    L.pad_to(k * C)
+    plants = {j * C + 16 + (j - 6) % 16: b"shk123 " for j in range(16)}
+    f = L.add(_blob(16 * C, plants))
+    want += [(f, "short", at + 6) for at in plants]
+    notes["body"] = (f, sorted(at + 6 for at in plants))
+    k += 16
+    L.pad_to(k * C)
+    plants, ends = {}, []
+    for j in range(16):
+        n = (j - 1) % 16                              # letters: the accept falls at 16*m + j
+        at = (2 * j + 1) * C - 4
+        plants[at] = b"bdk=" + b"m" * n + b"; "
+        ends.append(at + 4 + n + 1)
+    f = L.add(_blob(34 * C, plants))
+    want += [(f, "bounded", e) for e in ends]
+    notes["tail"] = (f, ends)
+    k += 34
+    L.pad_to(k * C)
+    plants = {2 * C - 1: b"awbk1234 ", 4 * C - 1: b" wbk1234 ", 6 * C - 1: b"\nwbk1234 "}
+    f = L.add(_blob(8 * C, plants))
+    want += [(f, "wb", 4 * C + 7), (f, "wb", 6 * C + 7)]
+    notes["ctx"] = (f, [2 * C, 4 * C, 6 * C])
+    k += 8
+    # filler chunks, so that no group's items reach half of the batch, then the last chunk
+    L.pad_to(3 * k * C)
+    f = L.add(_blob(C // 2, {4: b"shk123 "}))
+    want += [(f, "short", 10)]
+    notes["last"] = f
+    return L.batch(), sorted(want), notes
+
+
+def tail_batch(chunk, ext_cap):
+    """Tails of the list path under a follow-on cap of ext_cap bytes (cut: the first word
+    boundary at or behind it).  Every case is a file of its own that starts on a chunk
+    boundary, with its secret's literal in the last bytes of the file's first chunk.
+    Returns (batch, want, notes): the complete (file, rule id, end) triples (end WHOLE: the
+    rule's tail reached the cut, see with_group_mates) and the file of each named case."""
+    C = chunk
+    cut = (ext_cap + 15) // 16 * 16
+    L = _Files()
+    want, notes = [], {}
+
+    def case(name, content, triples):
+        L.pad_to((L.at + C - 1) // C * C + C)
+        f = L.add(content)
+        notes[name] = f
+        want.extend((f, r, e) for r, e in triples)
+
+    def bd(n, tail=b"; "):                            # chunk 0 ends with "bdk=", n letters follow
+        return _blob(C - 4, {}) + b"bdk=" + b"m" * n + tail
+    if cut > 24:
+        case("next chunk", bd(20) + fill(40), [("bounded", C + 21)])
+    # fe on the chunk's end: the match is complete at b >= fe, no tail
+    case("fe on chunk end", _blob(C, {C - 6: b"shk123"}), [("short", C)])
+    case("fe mid-word in a tail", bd(5, b""), [])
+    case("alive at fe, accepts at eot", bd(5, b";"), [("bounded", C + 6)])
+    case("eot rule at fe in a tail", _blob(C - 4, {}) + b"eokabcde", [("eot", C + 4)])
+    if cut < 300:  # (the default cap is far behind the longest `bounded` match)
+        # dies in the last word before the cut, its end on the last followed byte
+        case("ends on the last followed byte", bd(cut - 2) + fill(30), [("bounded", C + cut - 1)])
+        # alive at the cut: the rules over the whole file (";" would have ended it one byte later)
+        case("alive at the cut", bd(cut - 1) + fill(30), [("bounded", WHOLE)])
+    n = C + 30  # letters: over the whole next chunk, the end in the one behind it
+    assert n <= 300
+    case("crosses a whole chunk", bd(n) + fill(20), [("bounded", WHOLE if n >= cut else C + n + 1)])
+    case("immortal", _blob(C - 4, {}) + b"ubk{" + fill(40), [("unb", WHOLE)])
+    L.pad_to(3 * (L.at // C + 2) * C)
+    return L.batch(), sorted(want), notes
+
+
+ENTRY_COUNTS = (1, 2, 3, 5, 257, 512, 513)
+
+
+def entry_shape_batch(chunk, n):
+    """`short`'s list group with exactly n items: n files of one chunk each, on chunk
+    boundaries, each with one secret (a quad that is not full, lane 0's second chain alone at
+    257, the entry boundary at 512 / 513), between filler.  Returns (batch, want)."""
+    L = _Files()
+    want = []
+    for i in range(n):
+        L.pad_to((2 * i + 1) * chunk)
+        at = 3 + 7 * i % (chunk - 12)
+        f = L.add(_blob(chunk, {at: b"shk123 "}))
+        want.append((f, "short", at + 6))
+    L.pad_to((2 * n + 4) * chunk + 3)
+    return L.batch(), sorted(want)
+
+
+def named_triples(sc, triples):
+    """Expanded (file, rule, end) triples as sorted (file, rule id, end) tuples."""
+    ids = [r.ID for r in sc.Rules]
+    return sorted((int(f), ids[r], int(e)) for f, r, e in triples.tolist())
+
+
+def _sorted_triples(t):
+    import numpy as np
+    t = np.asarray(t, dtype=np.uint32).reshape(-1, 3)
+    return t[np.lexsort((t[:, 2], t[:, 1], t[:, 0]))]
+
+
+def _describe(sc, batch, chunk, tri):
+    """Where a triple lies: file, rule and group, chunk of the batch, offset in its word."""
+    f, r, e = (int(x) for x in tri)
+    rid = sc.Rules[r].ID if r < len(sc.Rules) else "?"
+    g = sc.rule_group(r) if r < len(sc.Rules) else -1
+    if f >= batch.nfiles:
+        return "file %d (not in the batch) rule %d (%s) end %d" % (f, r, rid, e)
+    if e == WHOLE:
+        return "file %d (%s) rule %d (%s) group %d: whole file" % (f, batch.path(f), r, rid, g)
+    p = int(batch.offsets[f]) + e
+    return "file %d (%s) end %d = batch byte %d: chunk %d, offset %d in its word; group %d rule %d (%s)" % (
+        f, batch.path(f), e, p, p // chunk, p % 16, g, r, rid)
+
+
+def _first_difference(a, b):
+    """(triple, 'missing' | 'extra') of the first triple in which the sorted multisets a (got)
+    and b (want) differ."""
+    i = j = 0
+    while i < len(a) and j < len(b):
+        x, y = tuple(a[i].tolist()), tuple(b[j].tolist())
+        if x == y:
+            i, j = i + 1, j + 1
+        elif x < y:
+            return a[i], "extra (not in the reference, or more often than there)"
+        else:
+            return b[j], "missing (in the reference, not on the device, or less often)"
+    if i < len(a):
+        return a[i], "extra (not in the reference, or more often than there)"
+    return b[j], "missing (in the reference, not on the device, or less often)"
+
+
+def check_candidates(dev, ref, batch, sc, chunk=256, skipped=False):
+    """K2's output as read back from the device (GpuContext.batch_candidates) against the
+    reference's raw records (Scanner.emulate_candidates with the context's settings).
+      count <= cand_cap: the expanded triples are equal as sorted arrays, duplicates kept
+        (the order of records is free); count is the reference's record count; no file has
+        flag 1.
+      count > cand_cap: exactly cand_cap records came back, their expansion is contained in
+        the reference's as a multiset, every file whose triples are not all present has
+        flag 1, and no file without a reference record has it.
+      Always: flag 4 is set for exactly the files with a record, flag 1 or flag 2 (for every
+        file when the rule set has host-only rules or K2 skipped a group: `skipped`), and the
+        keyword rows of those files are k1_reference's.
+    A failure names the first differing triple: file, chunk, offset in its word, group, rule."""
+    import numpy as np
+    rec, flags, kw = dev["records"], dev["flags"], dev["kw"]
+    count, cap = dev["count"], dev["cand_cap"]
+    ref = np.asarray(ref, dtype=np.uint32).reshape(-1, 3)
+    want = _sorted_triples(sc.expand_candidates(batch, ref))
+    got = _sorted_triples(sc.expand_candidates(batch, rec))
+    F = batch.nfiles
+    assert len(flags) == F and kw.shape[0] == F
+    if count <= cap:
+        if not np.array_equal(got, want):
+            tri, what = _first_difference(got, want)
+            raise AssertionError("K2 records differ from the reference (%d triples, %d in the reference): %s: %s" % (
+                len(got), len(want), what, _describe(sc, batch, chunk, tri)))
+        assert count == len(ref) == len(rec), (count, len(ref), len(rec))
+        bad = np.flatnonzero(flags & 1)
+        assert len(bad) == 0, "overflow flag without an overflow: file %d" % bad[0]
+    else:
+        assert len(rec) == cap, (len(rec), cap)
+        assert count == len(ref), (count, len(ref))
+        key = lambda t: (t[:, 0].astype(np.uint64) << np.uint64(44)) ^ (t[:, 1].astype(np.uint64) << np.uint64(32)) ^ t[:, 2]
+        gu, gc = np.unique(key(got), return_counts=True)
+        wu, wc = np.unique(key(want), return_counts=True)
+        at = np.searchsorted(wu, gu)
+        ok = (at < len(wu)) & (wu[np.minimum(at, len(wu) - 1)] == gu) if len(wu) else np.zeros(len(gu), bool)
+        ok[ok] &= gc[ok] <= wc[at[ok]]
+        if not ok.all():
+            k = gu[np.flatnonzero(~ok)[0]]
+            tri = got[np.flatnonzero(key(got) == k)[0]]
+            raise AssertionError("a record past the reference under overflow: extra: " + _describe(sc, batch, chunk, tri))
+        per_got = np.bincount(got[:, 0], minlength=F)
+        per_want = np.bincount(want[:, 0], minlength=F)
+        short = np.flatnonzero(per_got < per_want)
+        assert ((flags[short] & 1) != 0).all(), "a file with dropped records has no overflow flag: file %d" % (
+            short[(flags[short] & 1) == 0][0])
+        has_ref = np.bincount(ref[:, 0], minlength=F) > 0
+        bad = np.flatnonzero(((flags & 1) != 0) & ~has_ref)
+        assert len(bad) == 0, "overflow flag on a file without a reference record: file %d" % bad[0]
+    has_rec = np.bincount(rec[:, 0], minlength=F)[:F] > 0 if len(rec) else np.zeros(F, bool)
+    if count > cap:  # a dropped record also marks its file (hascand); the flag says which
+        has_rec |= (flags & 1) != 0
+    all_rows = skipped or sc.info()["n_hostonly"] > 0
+    row = np.ones(F, bool) if all_rows else has_rec | ((flags & 3) != 0)
+    bad = np.flatnonzero(((flags & 4) != 0) != row)
+    assert len(bad) == 0, "row-written flag of file %d is %d" % (bad[0], flags[bad[0]]) if len(bad) else ""
+    kw_ref, _ = sc.k1_reference(batch, chunk)
+    fb0 = sc.info()["n_keywords"] - 3  # the three fallback pseudo keywords: folding runes
+    fold = np.zeros(F, bool)
+    for k in range(fb0, fb0 + 3):
+        fold |= ((kw_ref[:, k // 32] >> np.uint32(k % 32)) & 1) != 0
+    bad = np.flatnonzero(((flags & 2) != 0) != fold)
+    assert len(bad) == 0, "folding-rune flag of file %d is %d" % (bad[0], flags[bad[0]]) if len(bad) else ""
+    bad = np.flatnonzero(row & (kw != kw_ref).any(axis=1))
+    assert len(bad) == 0, "keyword row of file %d: %s, reference %s" % (
+        bad[0], kw[bad[0]].tolist(), kw_ref[bad[0]].tolist()) if len(bad) else ""
+    return len(ref), len(want)
+
+
+def reference_output(sc, batch, chunk, ref, cand_cap=1 << 22, skipped=False):
+    """The device's output built from the reference alone, in batch_candidates' form (the
+    checker's own test): the first cand_cap records in reverse order, the flags and rows."""
+    import numpy as np
+    ref = np.asarray(ref, dtype=np.uint32).reshape(-1, 3)
+    F = batch.nfiles
+    kw, _ = sc.k1_reference(batch, chunk)
+    fb0 = sc.info()["n_keywords"] - 3
+    flags = np.zeros(F, dtype=np.uint8)
+    for k in range(fb0, fb0 + 3):
+        flags |= (((kw[:, k // 32] >> np.uint32(k % 32)) & 1) << 1).astype(np.uint8)
+    flags[np.unique(ref[cand_cap:, 0])] |= 1
+    mark = (flags != 0) | (np.bincount(ref[:, 0], minlength=F) > 0) | skipped | (sc.info()["n_hostonly"] > 0)
+    flags[mark] |= 4
+    rows = kw.copy()
+    rows[~mark] = 0
+    return {"count": len(ref), "cand_cap": cand_cap, "records": ref[:cand_cap][::-1].copy(), "flags": flags,
+            "kw": rows}

@@ -151,6 +151,8 @@ SIGNATURES = [
     ("tsg_batch_items", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,
                                   C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32),
                                   C.c_size_t, _U8P, C.c_size_t, _U64P]),
+    ("tsg_batch_candidates", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, _U8P,
+                                       C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
     ("tsg_batch_collect", C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),
@@ -200,6 +202,12 @@ SIGNATURES = [
                                               _U64P]),
     ("tsg_emulate_items", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.POINTER(C.c_uint32), C.c_size_t, _U64P, _U64P]),
+    ("tsg_emulate_candidates", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                         C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
+    ("tsg_emulate_item_candidates", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
+    ("tsg_expand_candidates", C.c_int, [_P, _P, _U64P, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,
+                                        C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
     ("tsg_layout_reference", C.c_int, [_U64P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
                                        _U8P, _U64P]),
     ("tsg_ruleset_rule_plan", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32),

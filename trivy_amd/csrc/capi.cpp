@@ -314,6 +314,70 @@ int tsg_emulate_items(const tsg_ruleset* rs, const uint8_t* data, const uint64_t
   }
 }
 
+int tsg_emulate_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                           uint32_t chunk, uint32_t ext_cap, uint64_t items_cap, uint32_t max_dense,
+                           uint32_t word_recs, uint32_t* records, size_t records_cap, uint64_t* n_records) {
+  if (!rs || !offsets || chunk == 0 || (!records && records_cap)) return fail(TSG_ERR_ARG, "bad argument");
+  try {
+    std::vector<uint64_t> poff(nfiles + 1, 0);
+    BatchView b{data, offsets, nfiles, "", poff.data()};
+    std::vector<Candidate> cand;
+    emulate_candidates(*rs->plan, b, chunk, ext_cap, items_cap, max_dense, word_recs != 0, &cand);
+    static_assert(sizeof(Candidate) == 3 * sizeof(uint32_t), "a record is three u32");
+    if (records) std::memcpy(records, cand.data(), sizeof(Candidate) * std::min(records_cap, cand.size()));
+    if (n_records) *n_records = cand.size();
+    return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(TSG_ERR_NOMEM, "out of memory");
+  } catch (const std::exception& ex) {
+    return fail(TSG_ERR_INTERNAL, ex.what());
+  }
+}
+
+int tsg_emulate_item_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                                uint32_t chunk, uint32_t ext_cap, uint32_t* triples, size_t triples_cap,
+                                uint64_t* n_triples) {
+  if (!rs || !offsets || chunk == 0 || (!triples && triples_cap)) return fail(TSG_ERR_ARG, "bad argument");
+  try {
+    std::vector<uint64_t> poff(nfiles + 1, 0);
+    BatchView b{data, offsets, nfiles, "", poff.data()};
+    KernelOutput ko;
+    EmuOptions eo;  // the device's every-chunk rule; no layout, no capacity
+    eo.max_back = kMaxBackChunks;
+    emulate_kernels(*rs->plan, b, chunk, ext_cap, &ko, nullptr, &eo);
+    // (TSG_EMU_WORDREC gives emulate_kernels' word records: candidates either way)
+    std::vector<Candidate> out;
+    for (const Candidate& c : ko.cand) expand_candidate(*rs->plan, b, c, &out);
+    if (triples) std::memcpy(triples, out.data(), sizeof(Candidate) * std::min(triples_cap, out.size()));
+    if (n_triples) *n_triples = out.size();
+    return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(TSG_ERR_NOMEM, "out of memory");
+  } catch (const std::exception& ex) {
+    return fail(TSG_ERR_INTERNAL, ex.what());
+  }
+}
+
+int tsg_expand_candidates(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                          const uint32_t* records, size_t n_records, uint32_t* triples, size_t triples_cap,
+                          uint64_t* n_triples) {
+  if (!rs || !offsets || (!records && n_records) || (!triples && triples_cap)) return fail(TSG_ERR_ARG, "bad argument");
+  try {
+    std::vector<uint64_t> poff(nfiles + 1, 0);
+    BatchView b{data, offsets, nfiles, "", poff.data()};
+    std::vector<Candidate> out;
+    for (size_t i = 0; i < n_records; i++)
+      expand_candidate(*rs->plan, b, Candidate{records[3 * i], records[3 * i + 1], records[3 * i + 2]}, &out);
+    if (triples) std::memcpy(triples, out.data(), sizeof(Candidate) * std::min(triples_cap, out.size()));
+    if (n_triples) *n_triples = out.size();
+    return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(TSG_ERR_NOMEM, "out of memory");
+  } catch (const std::exception& ex) {
+    return fail(TSG_ERR_INTERNAL, ex.what());
+  }
+}
+
 int tsg_layout_reference(const uint64_t* counts, uint32_t n_groups, uint64_t nchunks, uint64_t items_cap,
                          uint32_t max_dense, uint8_t* kind, uint64_t* totals) {
   if ((!counts && n_groups) || !kind) return fail(TSG_ERR_ARG, "bad argument");

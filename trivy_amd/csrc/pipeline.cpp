@@ -156,10 +156,14 @@ struct tsg_ctx {
   bool stopping = false;
   std::multiset<std::thread::id> slot_waiters;  // threads waiting in slot_take
   // the last tsg_batch_kernels: its lane, slot and the submission count after it
-  // (tsg_batch_items reads that lane while nothing else was enqueued since)
+  // (tsg_batch_items reads that lane while nothing else was enqueued since), and its output
+  // block and files (tsg_batch_candidates: the block is free again, and nothing takes or
+  // regrows a block without a submission, so it is intact while the count stands)
   LaneState* kernels_lane = nullptr;
   uint32_t kernels_slot = 0;
   uint64_t kernels_seq = 0;
+  int kernels_out = -1;
+  uint32_t kernels_nfiles = 0;
   // device-resident input: the fetch stream, the stats, and the last finished batch's
   // mirror (tsg_test_device_mirror)
   DeviceFetch* fetch = nullptr;
@@ -1436,6 +1440,8 @@ int tsg_batch_kernels(tsg_ctx* c, uint32_t slot_id, uint32_t nfiles, uint32_t* k
       c->kernels_lane = l;
       c->kernels_slot = slot_id;
       c->kernels_seq = c->seq;
+      c->kernels_out = oi;
+      c->kernels_nfiles = nfiles;
       if (kw) rc = lane_kw(l, kw, std::min(kw_len, W * nfiles));
       if (ev && !rc) rc = lane_events(l, ev, ev_len);
       if (const char* tp = getenv("TSG_K1F_TRACE")) {  // append K1F's per-wave trace (measurements)
@@ -1481,6 +1487,35 @@ int tsg_batch_items(tsg_ctx* c, uint32_t slot_id, uint32_t* entries, size_t entr
     if (dentries) std::memcpy(dentries, li.dentries.data(), 16 * std::min<size_t>(dentries_cap, n[1]));
     if (items) std::memcpy(items, li.items.data(), 8 * std::min<size_t>(items_cap, li.items.size() / 2));
     if (gskip) std::memcpy(gskip, li.gskip.data(), std::min(gskip_len, li.gskip.size()));
+    return TSG_OK;
+  });
+}
+
+int tsg_batch_candidates(tsg_ctx* c, uint32_t slot_id, uint32_t* records, size_t records_cap, uint8_t* flags,
+                         size_t flags_len, uint32_t* kw, size_t kw_len, uint64_t* n) {
+  if (!c || !n) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    std::lock_guard<std::mutex> g(c->m);
+    if (c->emulate) return fail(TSG_ERR_ARG, "an emulated context has no device output block");
+    if (!c->kernels_lane || c->kernels_slot != slot_id || c->kernels_seq != c->seq || c->kernels_out < 0)
+      return fail(TSG_ERR_ARG, "tsg_batch_candidates follows tsg_batch_kernels on the same slot");
+    // only what outputs_kernel wrote into the pinned block: its clamp, flags and sparse rows
+    const HostOut& ho = c->outs[c->kernels_out];
+    const uint32_t F = c->kernels_nfiles;
+    if (!ho.blk || ho.files_cap < F) return fail(TSG_ERR_INTERNAL, "the output block of the last tsg_batch_kernels is gone");
+    const size_t W = ho.kw_words;
+    const uint32_t nrec = std::min<uint32_t>(ho.counts[kCntCand], ho.cand_cap);
+    n[0] = ho.counts[kCntCand];
+    n[1] = nrec;
+    n[2] = F;
+    n[3] = ho.cand_cap;
+    if (records) std::memcpy(records, ho.cand, sizeof(Candidate) * std::min<size_t>(records_cap, nrec));
+    if (flags) std::memcpy(flags, ho.ovf, std::min<size_t>(flags_len, F));
+    if (kw)
+      for (uint32_t f = 0; f < F && (size_t)(f + 1) * W <= kw_len; f++) {
+        if (ho.ovf[f] & 4) std::memcpy(kw + (size_t)f * W, ho.kw + (size_t)f * W, sizeof(uint32_t) * W);
+        else std::memset(kw + (size_t)f * W, 0, sizeof(uint32_t) * W);
+      }
     return TSG_OK;
   });
 }

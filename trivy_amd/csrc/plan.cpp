@@ -934,6 +934,42 @@ std::vector<uint32_t> host_rules(const Plan& plan, const KernelOutputView& ko) {
   return out;
 }
 
+// one record's candidates into `out` (a word record replays its word from the batch)
+void expand_candidate(const Plan& plan, const BatchView& b, const Candidate& c, std::vector<Candidate>* out) {
+  if (!(c.rule & kCandTrans) || c.end == kCandWhole) {
+    out->push_back(c);
+    return;
+  }
+  const bool words = plan.groups.size() <= 0x3FFF;  // kCandWord records (kernels.hip accept_word)
+  const bool word = words && (c.rule & kCandWord);
+  const uint32_t g = (c.rule >> 16) & (words ? 0x3FFFu : 0x7FFFu), ix = c.rule & 0xFFFFu;
+  if (g >= plan.groups.size()) return;
+  const GroupPlan& gp = plan.groups[g];
+  const DFA& d = *gp.dfa;
+  const uint32_t ncd = (uint32_t)std::max(2, d.nclasses);  // the device's row width
+  if (word) {  // kCandWord: replay the word from row ix at byte `end` to the word's end
+    size_t st = ix / ncd;
+    if (st >= (size_t)d.nstates || c.file >= b.nfiles) return;
+    const uint64_t f0 = b.offsets[c.file], flen = b.offsets[c.file + 1] - f0;
+    const uint64_t pend = std::min<uint64_t>(flen, (((f0 + c.end) | 15) + 1) - f0);
+    for (uint64_t p = c.end; p < pend; p++) {
+      const size_t e = st * d.nclasses + d.cls[b.data[f0 + p]];
+      if (d.acc[e]) {
+        const auto& m = d.masks[d.acc[e]];
+        for (size_t k = 0; k < gp.rules.size(); k++)
+          if ((m[k / 64] >> (k % 64)) & 1) out->push_back({c.file, gp.rules[k], (uint32_t)p});
+      }
+      st = d.next[e];
+    }
+    return;
+  }
+  const size_t st = ix / ncd, cl = std::min<size_t>(ix % ncd, (size_t)d.nclasses - 1);
+  if (st >= (size_t)d.nstates) return;
+  const auto& m = d.masks[d.acc[st * d.nclasses + cl]];
+  for (size_t k = 0; k < gp.rules.size(); k++)
+    if ((m[k / 64] >> (k % 64)) & 1) out->push_back({c.file, gp.rules[k], c.end});
+}
+
 void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
                    const KernelOutputView& ko, int nthreads, BatchResult* out) {
   const uint32_t F = b.nfiles;
@@ -943,45 +979,10 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
   std::vector<Candidate> expanded;
   const Candidate* kc = ko.cand;
   size_t nkc = ko.ncand;
-  const bool words = plan.groups.size() <= 0x3FFF;  // kCandWord records (kernels.hip accept_word)
   {
     size_t ntrans = 0;
     for (size_t i = 0; i < nkc; i++) ntrans += (kc[i].rule & kCandTrans) && kc[i].end != kCandWhole;
     if (ntrans) {
-      // one record's candidates into `out` (a word record replays its word from the batch)
-      auto expand = [&](const Candidate& c, std::vector<Candidate>& out) {
-        if (!(c.rule & kCandTrans) || c.end == kCandWhole) {
-          out.push_back(c);
-          return;
-        }
-        const bool word = words && (c.rule & kCandWord);
-        const uint32_t g = (c.rule >> 16) & (words ? 0x3FFFu : 0x7FFFu), ix = c.rule & 0xFFFFu;
-        if (g >= plan.groups.size()) return;
-        const GroupPlan& gp = plan.groups[g];
-        const DFA& d = *gp.dfa;
-        const uint32_t ncd = (uint32_t)std::max(2, d.nclasses);  // the device's row width
-        if (word) {  // kCandWord: replay the word from row ix at byte `end` to the word's end
-          size_t st = ix / ncd;
-          if (st >= (size_t)d.nstates || c.file >= F) return;
-          const uint64_t f0 = b.offsets[c.file], flen = b.offsets[c.file + 1] - f0;
-          const uint64_t pend = std::min<uint64_t>(flen, (((f0 + c.end) | 15) + 1) - f0);
-          for (uint64_t p = c.end; p < pend; p++) {
-            const size_t e = st * d.nclasses + d.cls[b.data[f0 + p]];
-            if (d.acc[e]) {
-              const auto& m = d.masks[d.acc[e]];
-              for (size_t k = 0; k < gp.rules.size(); k++)
-                if ((m[k / 64] >> (k % 64)) & 1) out.push_back({c.file, gp.rules[k], (uint32_t)p});
-            }
-            st = d.next[e];
-          }
-          return;
-        }
-        const size_t st = ix / ncd, cl = std::min<size_t>(ix % ncd, (size_t)d.nclasses - 1);
-        if (st >= (size_t)d.nstates) return;
-        const auto& m = d.masks[d.acc[st * d.nclasses + cl]];
-        for (size_t k = 0; k < gp.rules.size(); k++)
-          if ((m[k / 64] >> (k % 64)) & 1) out.push_back({c.file, gp.rules[k], c.end});
-      };
       // In parallel, in record order: each word record's replay reads the batch at its own
       // place (a cache and TLB miss in a pinned multi-GiB slot), and serially that was half
       // of a layer piece's resolution (12-15 of ~28 Mcyc per 256 MiB piece, TSG_PROF).
@@ -992,7 +993,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
         auto& out = parts[bi];
         const size_t i1 = std::min(nkc, (bi + 1) * kRecBlk);
         out.reserve(i1 - bi * kRecBlk + 16);
-        for (size_t i = bi * kRecBlk; i < i1; i++) expand(kc[i], out);
+        for (size_t i = bi * kRecBlk; i < i1; i++) expand_candidate(plan, b, kc[i], &out);
       }, 1);
       size_t total = 0;
       for (const auto& pt : parts) total += pt.size();
@@ -1479,40 +1480,43 @@ void k1x_reference(const Plan& plan, const BatchView& bv, uint32_t chunk, std::v
   }
 }
 
-// The list kernel's output form for one item (kernels.hip k2_list_pair / Lane::tail with
-// word records): an accepting 16-B word (batch-aligned; its part inside [a, b) or the tail)
-// becomes one kCandWord record {file, group, row before its first byte, that byte's offset};
-// a tail stops at a word boundary past ext_cap or in an immortal state (kCandWhole for the
-// group's rules); end-of-text accepts are per-rule candidates.  TSG_EMU_WORDREC selects it
-// (tests: it drives resolve_batch's word expansion without a device).
-static void emulate_words(const DFA& d, uint32_t gi, const std::vector<uint32_t>& rules, const uint8_t* data,
-                          uint32_t f, uint64_t fs, uint64_t fe, uint64_t a, uint64_t b, uint32_t ext_cap,
-                          std::vector<Candidate>* out) {
+// K2's output form for one segment [a, b) of file [fs, fe) and the tail behind it (kernels.hip
+// k2_list_pair, Lane::piece / streams, Lane::tail).  A word is 16 bytes of the batch, its part
+// inside the segment or the tail.  In word form an accepting word becomes one kCandWord record
+// {file, group, row before its first byte, that byte's offset}; in transition form every
+// accepting transition becomes one kCandTrans record {file, group, row + class, its offset}.
+// A tail stops at a word boundary past ext_cap or in an immortal state (kCandWhole for the
+// group's rules); end-of-text accepts are per-rule candidates.  The list kernel at chunk sizes
+// of whole 128-byte lines writes words for body and tail (TSG_EMU_WORDREC selects that form in
+// emulate_kernels: it drives resolve_batch's word expansion without a device).
+static void emulate_records(const DFA& d, uint32_t gi, const std::vector<uint32_t>& rules, const uint8_t* data,
+                            uint32_t f, uint64_t fs, uint64_t fe, uint64_t a, uint64_t b, uint32_t ext_cap,
+                            bool body_words, bool tail_words, std::vector<Candidate>* out) {
   const uint32_t nc = (uint32_t)d.nclasses, ncd = std::max<uint32_t>(2, nc);
-  auto word_rec = [&](uint32_t s0, uint64_t p0) {
-    out->push_back({f, kCandTrans | kCandWord | (gi << 16) | (s0 * ncd), (uint32_t)(p0 - fs)});
-  };
   auto eot = [&](uint32_t s) {
     if (!d.eot_acc[s]) return;
     const auto& m = d.masks[d.eot_acc[s]];
     for (size_t k = 0; k < rules.size(); k++)
       if ((m[k / 64] >> (k % 64)) & 1) out->push_back({f, rules[k], (uint32_t)(fe - fs)});
   };
-  // bytes [p, e) of one word from state s: the state after them, accept seen
-  auto step = [&](uint32_t& s, uint64_t p, uint64_t e) {
+  // bytes [p, e) of one word from state s: the state after them, the word's records
+  auto step = [&](uint32_t& s, uint64_t p, uint64_t e, bool words) {
+    const uint32_t s0 = s;
+    const uint64_t p0 = p;
     bool acc = false;
     for (; p < e; p++) {
-      const size_t x = (size_t)s * nc + d.cls[data[p]];
+      const uint32_t c = d.cls[data[p]];
+      const size_t x = (size_t)s * nc + c;
+      if (d.acc[x] && !words) out->push_back({f, kCandTrans | (gi << 16) | (s * ncd + c), (uint32_t)(p - fs)});
       acc |= d.acc[x] != 0;
       s = d.next[x];
     }
-    return acc;
+    if (acc && words) out->push_back({f, kCandTrans | kCandWord | (gi << 16) | (s0 * ncd), (uint32_t)(p0 - fs)});
   };
   uint32_t s = (a == fs) ? d.start[kCtxBOT] : d.start[DFA::ctx_of(data[a - 1], d)];
   for (uint64_t p = a; p < b;) {
     const uint64_t e = std::min<uint64_t>(b, (p | 15) + 1);
-    const uint32_t s0 = s;
-    if (step(s, p, e)) word_rec(s0, p);
+    step(s, p, e, body_words);
     p = e;
   }
   if (b >= fe) {
@@ -1527,8 +1531,7 @@ static void emulate_words(const DFA& d, uint32_t gi, const std::vector<uint32_t>
       return;
     }
     const uint64_t e = std::min<uint64_t>(fe, (q | 15) + 1);
-    const uint32_t s0 = s;
-    if (step(s, q, e)) word_rec(s0, q);
+    step(s, q, e, tail_words);
     q = e;
   }
   if (q >= fe && !d.dead[s]) eot(s);
@@ -1614,7 +1617,7 @@ void emulate_kernels(const Plan& plan, const BatchView& bv, uint32_t chunk, uint
     const uint64_t a = std::max<uint64_t>(fs, c * chunk), b = std::min<uint64_t>(fe, (c + 1) * chunk);
     if (group_item_bytes) (*group_item_bytes)[gi] += b - a;
     if (word_recs) {
-      emulate_words(d, gi, g.rules, bv.data, f, fs, fe, a, b, ext_cap, &ko->cand);
+      emulate_records(d, gi, g.rules, bv.data, f, fs, fe, a, b, ext_cap, true, true, &ko->cand);
       return;
     }
     bool o = run_segment(d, bv.data, fs, fe, a, b, ext_cap, [&](uint32_t mi, uint64_t pos) {
@@ -1633,6 +1636,65 @@ void emulate_kernels(const Plan& plan, const BatchView& bv, uint32_t chunk, uint
     ko->cand.resize((size_t)opt->cand_cap);
   }
   if (st) *st = es;
+}
+
+void emulate_candidates(const Plan& plan, const BatchView& bv, uint32_t chunk, uint32_t ext_cap, uint64_t items_cap,
+                        uint32_t max_dense, bool word_recs, std::vector<Candidate>* out) {
+  const uint32_t F = bv.nfiles;
+  const size_t G = plan.groups.size();
+  const uint64_t total = bv.offsets[F];
+  const bool words = word_recs && G <= 0x3FFF;
+  const bool fast_list = (chunk & 127) == 0;  // k2_list_pair's word loop; Lane::piece otherwise
+  std::vector<uint32_t> kw, ev;
+  k1_reference(plan, bv, chunk, &kw, &ev);
+  std::vector<uint64_t> counts(G, 0);
+  emulate_items(plan, bv, chunk, kw.data(), ev, kMaxBackChunks, [&](uint32_t g, uint32_t, uint64_t) { counts[g]++; });
+  std::vector<uint8_t> kind(G, kGroupNone);
+  layout_reference(counts.data(), (uint32_t)G, ev.size(), items_cap, max_dense, kind.data(), nullptr);
+  out->clear();
+  // list groups: one segment per item, the tail behind it capped at ext_cap
+  emulate_items(plan, bv, chunk, kw.data(), ev, kMaxBackChunks, [&](uint32_t gi, uint32_t f, uint64_t c) {
+    if (kind[gi] != kGroupList) return;
+    const GroupPlan& g = plan.groups[gi];
+    const uint64_t fs = bv.offsets[f], fe = bv.offsets[f + 1];
+    const uint64_t a = std::max<uint64_t>(fs, c * chunk), b = std::min<uint64_t>(fe, (c + 1) * chunk);
+    emulate_records(*g.dfa, gi, g.rules, bv.data, f, fs, fe, a, b, ext_cap, words && fast_list, words, out);
+  });
+  // dense groups (k2_dense_entry): every lane range of kStreams chunks; a range inside one
+  // file is kStreams segments of a chunk each (Lane::streams), otherwise each file's part of
+  // the range is one segment (Lane::piece); bodies in transition form
+  constexpr uint64_t kStreams = 4;
+  for (uint32_t gi = 0; gi < G; gi++) {
+    if (kind[gi] != kGroupDense) continue;
+    const GroupPlan& g = plan.groups[gi];
+    auto gated = [&](uint32_t f) {
+      if (g.always) return true;
+      for (int w = 0; w < plan.kw_words; w++)
+        if (kw[(size_t)f * plan.kw_words + w] & g.kwmask[w]) return true;
+      return false;
+    };
+    auto segment = [&](uint32_t f, uint64_t a, uint64_t b) {
+      emulate_records(*g.dfa, gi, g.rules, bv.data, f, bv.offsets[f], bv.offsets[f + 1], a, b, ext_cap, false, words, out);
+    };
+    uint32_t f = 0;
+    for (uint64_t a = 0; a < total; a += kStreams * chunk) {
+      const uint64_t b = std::min<uint64_t>(a + kStreams * chunk, total);
+      while (bv.offsets[f + 1] <= a) f++;  // the file of byte a
+      if (b == a + kStreams * chunk && b <= bv.offsets[f + 1]) {
+        if (gated(f))
+          for (uint64_t i = 0; i < kStreams; i++) segment(f, a + i * chunk, a + (i + 1) * chunk);
+        continue;
+      }
+      uint32_t h = f;
+      for (uint64_t p = a; p < b; h++) {
+        const uint64_t fe = bv.offsets[h + 1];
+        if (fe <= p) continue;
+        const uint64_t se = std::min(b, fe);
+        if (gated(h)) segment(h, p, se);
+        p = se;
+      }
+    }
+  }
 }
 
 }  // namespace tsg

@@ -259,6 +259,33 @@ void emulate_kernels(const Plan& plan, const BatchView& b, uint32_t chunk, uint3
                      KernelOutput* ko, std::vector<uint64_t>* group_item_bytes = nullptr,
                      const EmuOptions* opt = nullptr, EmuStats* st = nullptr);
 
+// What K2 writes for one batch, record by record, in the device's own form and under the
+// device's rules (tests: compared with the records read back from the device).  Items come
+// from emulate_items(max_back = kMaxBackChunks) and the kinds from layout_reference; a
+// skipped group has no records.
+//   list group, chunk a multiple of 128 (k2_list_pair's word loop): per item, one kCandWord
+//     record per accepting 16-B word of the body and of the tail
+//   list group, other chunk sizes (Lane::piece): the body writes one kCandTrans record per
+//     accepting transition, the tail word records
+//   dense group (k2_dense_entry): every lane range of 4 consecutive chunks of the batch; a
+//     range that lies in one gated file is four segments of a chunk, each with its own tail
+//     (Lane::streams), otherwise each gated file's part of the range is one segment with one
+//     tail (Lane::piece); bodies write transition records, tails word records
+//   word_recs = false (the k2_no_word_recs knob; always with 16,384 groups and more): every
+//     word record above is the word's transition records instead (Lane::replay_emit)
+// Everywhere: end-of-text accepts are per-rule candidates {file, rule, file length}, and a
+// tail alive at a word boundary >= ext_cap bytes behind its segment, or in an immortal state,
+// ends with {file, rule, kCandWhole} for every rule of the group.  No capacity is applied.
+void emulate_candidates(const Plan& plan, const BatchView& b, uint32_t chunk, uint32_t ext_cap, uint64_t items_cap,
+                        uint32_t max_dense, bool word_recs, std::vector<Candidate>* out);
+
+// The candidates of one K2 record appended to out: a plain candidate (kCandWhole included)
+// as it is, a transition record as one candidate per rule of its accept mask, a word record
+// as the candidates of every accepting transition from its byte to the end of its 16-B word
+// of the batch (or of the file).  A record that names no group, state or file of the plan
+// and batch gives nothing.
+void expand_candidate(const Plan& plan, const BatchView& b, const Candidate& c, std::vector<Candidate>* out);
+
 // The item set K2 scans, given K1's output (kw [nfiles * kw_words], ev [chunks]): visit(g, f,
 // c) for every group g, file f and chunk c, in that order, such that g is gated for f
 // (always, or kw & kwmask), c is a chunk of f, and some chunk in [c, min(c + back_g, last

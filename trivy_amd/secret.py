@@ -228,6 +228,11 @@ class Batch:
             "utf-8", "surrogateescape")
 
 
+DEFAULT_EXT_CAP, DEFAULT_CAND_CAPACITY = 1 << 16, 1 << 22  # tsg_ctx_options' defaults
+# K2 record forms (include/trivy_secret.h, tsg_emulate_candidates)
+CAND_WHOLE, CAND_TRANS, CAND_WORD = 0xFFFFFFFF, 0x80000000, 0x40000000
+
+
 class Scanner:
     """secret.Scanner{Global}: compiled once, shared read-only (thread-safe natively)."""
 
@@ -310,6 +315,47 @@ class Scanner:
         N.check(N.lib().tsg_emulate_items(*args, tri.ctypes.data_as(C.POINTER(C.c_uint32)), n.value,
                                           None, None))
         return tri[:n.value], counts[:G]
+
+    def emulate_candidates(self, batch, chunk, ext_cap=DEFAULT_EXT_CAP, items_cap=None, max_dense=16,
+                           word_recs=True):
+        """What K2 should write for the batch (tsg_emulate_candidates): raw records [n, 3]
+        {file, rule, end} in the device's form, no capacity applied.  items_cap None is the
+        default capacity of the batch's chunk count."""
+        if items_cap is None:
+            items_cap = default_items_cap((int(batch.offsets[-1]) + chunk - 1) // chunk)
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        args = (self.handle, C.c_void_p(batch.data.ctypes.data), batch.offsets.ctypes.data_as(u64p),
+                batch.nfiles, chunk, int(ext_cap), int(items_cap), int(max_dense), 1 if word_recs else 0)
+        n = C.c_uint64()
+        N.check(N.lib().tsg_emulate_candidates(*args, None, 0, C.byref(n)))
+        rec = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
+        N.check(N.lib().tsg_emulate_candidates(*args, rec.ctypes.data_as(u32p), n.value, None))
+        return rec[:n.value]
+
+    def emulate_item_candidates(self, batch, chunk, ext_cap=DEFAULT_EXT_CAP):
+        """(file, rule, end) triples [n, 3] of the emulation's per-item form
+        (tsg_emulate_item_candidates), in item order."""
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        args = (self.handle, C.c_void_p(batch.data.ctypes.data), batch.offsets.ctypes.data_as(u64p),
+                batch.nfiles, chunk, int(ext_cap))
+        n = C.c_uint64()
+        N.check(N.lib().tsg_emulate_item_candidates(*args, None, 0, C.byref(n)))
+        tri = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
+        N.check(N.lib().tsg_emulate_item_candidates(*args, tri.ctypes.data_as(u32p), n.value, None))
+        return tri[:n.value]
+
+    def expand_candidates(self, batch, records):
+        """K2 records -> (file, rule, end) triples [n, 3] as the resolver expands them
+        (tsg_expand_candidates), in record order, CAND_WHOLE ends kept."""
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 3)
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        args = (self.handle, C.c_void_p(batch.data.ctypes.data), batch.offsets.ctypes.data_as(u64p),
+                batch.nfiles, rec.ctypes.data_as(u32p), len(rec))
+        n = C.c_uint64()
+        N.check(N.lib().tsg_expand_candidates(*args, None, 0, C.byref(n)))
+        tri = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
+        N.check(N.lib().tsg_expand_candidates(*args, tri.ctypes.data_as(u32p), n.value, None))
+        return tri[:n.value]
 
     def candidate_stats(self, batch, chunk):
         """tsg_emulate_candidate_stats: (candidate ends per rule, K2 item bytes per group)."""
@@ -561,6 +607,29 @@ class GpuContext:
                                         gskip.ctypes.data_as(u8p), G, m))
         assert list(m) == list(n)
         return ent[:n[0]], dent[:n[1]], items[:n[2]], gskip[:G]
+
+    def batch_candidates(self):
+        """What K2 and the outputs kernel of the last kernels() call handed to the host
+        (tsg_batch_candidates): {"count": records K2 reserved, "cand_cap": the capacity,
+        "records": [min(count, cand_cap), 3] raw {file, rule, end}, "flags": [nfiles] (1
+        overflow, 2 folding runes, 4 row written), "kw": [nfiles, kw_words] the rows of the
+        files with flag 4, zero elsewhere}."""
+        sid, b = self._upload
+        W = (self.scanner.info()["n_keywords"] + 31) // 32
+        n = (C.c_uint64 * 4)()
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        N.check(N.lib().tsg_batch_candidates(self._h, sid, None, 0, None, 0, None, 0, n))
+        assert n[2] == b.nfiles
+        rec = np.zeros((max(n[1], 1), 3), dtype=np.uint32)
+        flags = np.zeros(max(b.nfiles, 1), dtype=np.uint8)
+        kw = np.zeros(max(b.nfiles * W, 1), dtype=np.uint32)
+        m = (C.c_uint64 * 4)()
+        N.check(N.lib().tsg_batch_candidates(self._h, sid, rec.ctypes.data_as(u32p), n[1],
+                                             flags.ctypes.data_as(u8p), b.nfiles,
+                                             kw.ctypes.data_as(u32p), b.nfiles * W, m))
+        assert list(m) == list(n)
+        return {"count": int(n[0]), "cand_cap": int(n[3]), "records": rec[:n[1]],
+                "flags": flags[:b.nfiles], "kw": kw[:b.nfiles * W].reshape(b.nfiles, W)}
 
     def k1_output(self, chunk):
         """(keyword bits [nfiles, kw_words], chunk event bits) of the last kernels() call."""
