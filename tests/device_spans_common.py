@@ -133,7 +133,7 @@ def check_scan(ctx, lay, dev, gate=True, mirror=True, wrapper=True):
     assert st["sum_bytes_in"] == before["sum_bytes_in"] + st["bytes_in"]
     assert di["whole_batch_copy"] == 0 and di["stage_ms"] == st["gather_ms"]
     if mirror:
-        check_mirror(ctx, b, di)
+        check_mirror(ctx, b, di, src=lay.starts[want_kept])
     found = S.decode_results(want, [b.path(i) for i in range(b.nfiles)], ctx.scanner.Rules)
     if wrapper:
         res, kept2 = ctx.scan_spans(dev.tensor, lay.starts, lay.lengths, lay.paths, binary_gate=gate)

@@ -7,6 +7,9 @@
 //   2. tsg_batch_upload + tsg_slot_submit + tsg_batch_collect(ticket) from 16 threads
 //   3. tsg_queue_scan: 16 threads, one file per call (analyzer.go:419-443)
 //   4. tsg_multi_scan_batch over 3 contexts from 4 threads (image.go:210-234)
+//   5. tsg_layer_scan / tsg_fs_scan from 8 threads on one context
+//   6. tsg_device_submit / tsg_scan_device and tsg_device_spans_submit / tsg_scan_device_spans,
+//      a thread each, on one context
 //
 // usage: stress RULES CORPUS_DIR    (files written by tests/test_sanitizers.py)
 //   RULES: one rule per line, fields separated by \x1f: id, category, title, severity,
@@ -135,8 +138,10 @@ int main(int argc, char** argv) {
   const uint64_t* poff = (const uint64_t*)poffb.data();
   const uint32_t nfiles = (uint32_t)(offb.size() / 8 - 1);
   std::vector<Batch> batches;
+  std::vector<uint32_t> first;  // the corpus file each batch starts at
   for (uint32_t f = 0, k = 0; f < nfiles; k++) {
     Batch b;
+    first.push_back(f);
     const uint32_t want = 1 + (k * 7) % 23;
     for (uint32_t j = 0; j < want && f < nfiles; j++, f++)
       b.add(data.data() + off[f], off[f + 1] - off[f], paths.data() + poff[f], poff[f + 1] - poff[f]);
@@ -278,6 +283,46 @@ int main(int argc, char** argv) {
     tsg_ctx_destroy(c2);
   }
   std::printf("pipelined scans done\n");
+  // 6. input in "device" memory (host memory for an emulated context) from two threads on one
+  // context: one submits every batch packed (tsg_device_submit + collect, then
+  // tsg_scan_device), the other the same files as spans of the corpus (gate off: all are
+  // kept; tsg_device_spans_submit + collect, then tsg_scan_device_spans)
+  {
+    tsg_ctx* c3 = nullptr;
+    if (tsg_ctx_create(0, rs, &o, &c3)) return 2;
+    threads(2, [&](int t) {
+      for (size_t i = 0; i < batches.size(); i++) {
+        const Batch& b = batches[i];
+        const uint64_t* starts = off + first[i];
+        std::vector<uint64_t> lengths(b.n());
+        for (uint32_t j = 0; j < b.n(); j++) lengths[j] = b.off[j + 1] - b.off[j];
+        uint64_t tk = 0;
+        tsg_result *r1 = nullptr, *r2 = nullptr;
+        const char* what = t == 0 ? "device batch" : "spans batch";
+        // (a submitted ticket is collected whatever comes after it, so that nothing stays pending)
+        if (t == 0 ? tsg_device_submit(c3, b.data.data(), b.off.data(), b.n(), b.paths.data(), b.poff.data(), &tk)
+                   : tsg_device_spans_submit(c3, data.data(), data.size(), starts, lengths.data(), b.n(), b.paths.data(),
+                                             b.poff.data(), 0, nullptr, &tk)) {
+          check(false, what, (int)i);
+          continue;
+        }
+        const int rc2 =
+            t == 0 ? tsg_scan_device(c3, b.data.data(), b.off.data(), b.n(), b.paths.data(), b.poff.data(), &r2)
+                   : tsg_scan_device_spans(c3, data.data(), data.size(), starts, lengths.data(), b.n(), b.paths.data(),
+                                           b.poff.data(), 0, nullptr, &r2);
+        if (tsg_batch_collect(c3, tk, &r1) || rc2) {
+          check(false, what, (int)i);
+          if (r1) tsg_result_free(r1);
+          if (r2) tsg_result_free(r2);
+          continue;
+        }
+        check(take(r1) == want[i] && take(r2) == want[i], t == 0 ? "device batch result" : "spans batch result", (int)i);
+      }
+    });
+    check(tsg_batch_pending(c3) == 0, "nothing pending after device-resident batches", 0);
+    tsg_ctx_destroy(c3);
+  }
+  std::printf("device-resident input done\n");
   tsg_ruleset_destroy(rs);
   std::printf(g_fail ? "FAILED %d\n" : "OK\n", g_fail.load());
   return g_fail ? 1 : 0;

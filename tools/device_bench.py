@@ -20,7 +20,8 @@ resident path, and the share of the bytes that was fetched.  The two paths are t
 alternation, --rounds windows of --steps passes each after --warmup passes, with the host
 clock over whole windows (every result collected); the line carries every window's GB/s
 and the medians.  The per-stage figures are the library's HIP-event times of the last
-window (tsg_stats, tsg_device_input_stats).
+window (tsg_stats, tsg_device_input_stats); resident_windows_ms has the stage's and the
+fetch's mean of every window.
 
 --spans measures tsg_device_spans_submit instead (GpuContext.scan_spans' entry point).  The
 seeded corpus is laid out as a decompressed layer would be: the files in order with 512
@@ -175,12 +176,15 @@ def main():
         return kept, dt, ds, dd
 
     pgbs, rgbs, equal = [], [], True
+    win = {"stage": [], "fetch": []}  # HIP-event means per batch of each resident window
     for _ in range(max(1, args.rounds)):
         pk, pdt, ps, _ = timed(submit_pcie)
         rk, rdt, rs, rd = timed(submit_resident)
         equal = equal and all(pk[i] == rk[i] for i in range(len(slots)))
         pgbs.append(round(total * args.steps / pdt / 1e9, 3))
         rgbs.append(round(total * args.steps / rdt / 1e9, 3))
+        win["stage"].append(round(rs["sum_h2d_ms"] / max(1, rs["batches"]), 4))
+        win["fetch"].append(round(rd["sum_fetch_ms"] / max(1, rs["batches"]), 4))
     nbat = max(1, rs["batches"])
     pbat = max(1, ps["batches"])
     line = {
@@ -197,6 +201,7 @@ def main():
             "k1": round(rs["sum_k1_ms"] / nbat, 3), "gates": round(rs["sum_gate_ms"] / nbat, 3),
             "k2": round(rs["sum_k2_ms"] / nbat, 3), "resolve": round(rs["sum_resolve_ms"] / nbat, 3),
             "wall": round(rdt / args.steps / len(slots) * 1e3, 3)},
+        "resident_windows_ms": win,
         "pcie_per_batch_ms": {
             "h2d": round(ps["sum_h2d_ms"] / pbat, 3), "k1": round(ps["sum_k1_ms"] / pbat, 3),
             "resolve": round(ps["sum_resolve_ms"] / pbat, 3),

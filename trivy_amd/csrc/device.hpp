@@ -6,13 +6,17 @@
 // of a batch on that stream with no host round trip:
 //
 //   H2D (pinned slot -> HBM; for a device-resident batch stage_kernel, caller's HBM -> lane
-//   buffer, or gather_kernel for files given as spans of the caller's buffer) and one H2D of the file offsets  prep (zero fills, coarse file
-//   map)  K1  keyword gates  event-chunk compaction  item counts  item layout
-//   (device-side)  item lists  K2  outputs (candidates, keyword bits, overflow / skip
-//   flags, counters: written straight into pinned, host-mapped memory)
+//   buffer, or gather_kernel for files given as spans of the caller's buffer) and one H2D of
+//   the file offsets  prep (zero fills, coarse file map)  K1  keyword gates  event-chunk
+//   compaction  item counts  item layout (device-side)  item lists  K2  outputs (candidates,
+//   keyword bits, overflow / skip flags, counters: written straight into pinned, host-mapped
+//   memory)
 //
 // and records the batch's completion event.  Two lanes per device let the H2D of one batch
-// overlap the kernels of the other.
+// overlap the kernels of the other.  The files of a device-resident batch that the host
+// resolver reads come to the pinned slot afterwards, on the context's fetch stream
+// (DeviceFetch): fetch_kernel (gather_kernel for spans), or one runtime D2H when every file of
+// a packed batch is needed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -88,7 +92,7 @@ struct K2Diag {
 
 // A segment of a gather (gather_kernel): `len` bytes at offset `src` of the caller's buffer
 // go to offset `dst` of the destination.  The host lists them (files merged only where they
-// are adjacent in both buffers, each cut to kFetchSegBytes).
+// are adjacent in both buffers, each cut to kGatherSegBytes).
 struct GatherSeg {
   uint64_t src, dst, len;
 };
@@ -174,24 +178,22 @@ int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out);
 int lane_k1f_trace(LaneState* l, std::vector<unsigned long long>* out);  // TSG_K1F_TRACE
 
 // ---- device-resident input: the fetch of the files the host resolver reads
-// A byte range of a batch.  The host lists the ranges of the needed files (adjacent files
-// merged, each range cut to kFetchSegBytes so that one very large file spreads over many
-// blocks) and fetch_kernel copies them from the caller's buffer into the batch's pinned slot
-// at the same offsets.
-struct FetchSeg {
-  uint64_t off, len;
-};
-constexpr uint64_t kFetchSegBytes = 64u << 10;
+// The host lists the needed files as gather segments (adjacent files merged, each run cut to
+// kGatherSegBytes so that one very large file spreads over many blocks).  A packed batch's
+// have src == dst: fetch_kernel copies them from the caller's buffer into the batch's pinned
+// slot at the same offsets.  A spans batch's go through gather_kernel, their source the
+// files' spans.
+constexpr uint64_t kGatherSegBytes = 64u << 10;
 // The context's fetch stream (not a lane's: a lane may already run a later batch), its
 // events and the pinned segment list.  Calls are serialized inside.
 struct DeviceFetch;
 int fetch_create(DeviceRules* d, DeviceFetch** out);
 void fetch_destroy(DeviceFetch* f);
-// host_dst[seg) = d_src[seg) for every listed segment of the `total` bytes at d_src;
-// host_dst is pinned, device-visible memory (a slot's data).  Synchronous; *ms = the
-// kernel's HIP-event time.
+// host_dst[seg.dst, +len) = d_src[seg.dst, +len) for every listed segment (each with src ==
+// dst) of the `total` bytes at d_src; host_dst is pinned, device-visible memory (a slot's
+// data).  Synchronous; *ms = the kernel's HIP-event time.
 int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst,
-                   const FetchSeg* segs, size_t nsegs, float* ms);
+                   const GatherSeg* segs, size_t nsegs, float* ms);
 // Spans of a device buffer: flags[f] = utils.IsBinary of the span {starts[f], lengths[f]} of
 // the base_bytes bytes at d_base (binary_gate_kernel on the fetch stream).  The three arrays
 // are device addresses of pinned, host-mapped memory; the host has checked every span

@@ -47,7 +47,7 @@ struct PinBuf {
 };
 void ctx_pin_give(tsg_ctx* c, PinBuf* b);
 // dst->p = the listed {offset, length} ranges of the base_bytes bytes at d_base, back to back
-// in list order (gather_kernel: adjacent ranges merge, segments are cut to kFetchSegBytes;
+// in list order (gather_kernel: adjacent ranges merge, segments are cut to kGatherSegBytes;
 // memcpy of the same segments when emulated).  Every range lies inside the buffer.
 int ctx_fetch_ranges(tsg_ctx* c, const void* d_base, uint64_t base_bytes,
                      const std::pair<uint64_t, uint64_t>* ranges, size_t n, PinBuf* dst);

@@ -340,7 +340,10 @@ __global__ void __launch_bounds__(256) stage_kernel(uint8_t* __restrict__ dst, c
 }
 
 // segments {offset, length} of the caller's batch into the pinned slot's host-mapped data at
-// the same offsets, a block per segment (the host cuts them to kFetchSegBytes)
+// the same offsets, a block per segment (the host cuts them to kGatherSegBytes)
+struct FetchSeg {
+  uint64_t off, len;
+};
 struct FetchArgs {
   const uint8_t* src;     // the caller's buffer, `total` bytes
   uint8_t* dst;           // device address of the slot's data
@@ -392,7 +395,7 @@ __global__ void __launch_bounds__(256) binary_gate_kernel(SpanGateArgs A) {
 }
 
 // gather_kernel copies segments {src, dst, len} of the caller's buffer to dst + seg.dst, a
-// block per segment (the host cuts them to kFetchSegBytes; source and destination alignment
+// block per segment (the host cuts them to kGatherSegBytes; source and destination alignment
 // differ per segment, copy_span's shift is uniform per call).  NT: into the lane buffer in
 // stage_kernel's place, the kept files back to back; !NT: the files the resolver reads into
 // the pinned mirror at their compacted offsets.  A segment that leaves either buffer is
@@ -4147,16 +4150,43 @@ int fetch_create(DeviceRules* d, DeviceFetch** out) {
 
 void fetch_destroy(DeviceFetch* f) { delete f; }
 
-int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, const FetchSeg* segs,
+// A call on the fetch stream holds the lock with the device set.  Nothing of an earlier call
+// is in flight (each waits before it returns), so the call may regrow what a kernel reads.
+struct FetchCall {
+  std::lock_guard<std::mutex> g;
+  int rc;
+  explicit FetchCall(DeviceFetch* f)
+      : g(f->m), rc(hipSetDevice(f->d->device) == hipSuccess ? TSG_OK : fail(TSG_ERR_GPU, "hipSetDevice failed")) {}
+};
+
+// `work` is enqueued between the two events and `behind` after them; then the host waits for
+// ev[1]: a default event, with a system fence, so what the work wrote to host memory is
+// visible.  *ms = the work's HIP-event time.
+template <class Work, class Behind>
+int fetch_run(DeviceFetch* f, float* ms, Work work, Behind behind) {
+  HIP_TRY(hipEventRecord(f->ev[0], f->st));
+  if (int rc = work()) return rc;
+  HIP_TRY(hipEventRecord(f->ev[1], f->st));
+  if (int rc = behind()) return rc;
+  HIP_TRY(hipEventSynchronize(f->ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  return TSG_OK;
+}
+template <class Work>
+int fetch_run(DeviceFetch* f, float* ms, Work work) {
+  return fetch_run(f, ms, work, [] { return (int)TSG_OK; });
+}
+
+int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, const GatherSeg* segs,
                    size_t nsegs, float* ms) {
   *ms = 0;
   if (!nsegs) return TSG_OK;
   if (nsegs > 0xFFFFFFFFu) return fail(TSG_ERR_INTERNAL, "too many fetch segments");
   for (size_t k = 0; k < nsegs; k++)  // the kernel writes host memory: nothing outside the batch
-    if (segs[k].off > total || segs[k].len > total - segs[k].off)
+    if (segs[k].src != segs[k].dst || segs[k].dst > total || segs[k].len > total - segs[k].dst)
       return fail(TSG_ERR_INTERNAL, "fetch segment outside the batch");
-  std::lock_guard<std::mutex> g(f->m);
-  HIP_TRY(hipSetDevice(f->d->device));
+  FetchCall call(f);
+  if (call.rc) return call.rc;
   if (f->segs_cap < nsegs) {
     if (f->segs) HIP_TRY(hipHostFree(f->segs));
     f->segs = nullptr;
@@ -4166,38 +4196,30 @@ int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t
     HIP_TRY(hipHostGetDevicePointer((void**)&f->segs_dev, f->segs, 0));
     f->segs_cap = cap;
   }
-  std::memcpy(f->segs, segs, sizeof(FetchSeg) * nsegs);
-  FetchArgs A{};
-  A.src = d_src;
+  for (size_t k = 0; k < nsegs; k++) f->segs[k] = FetchSeg{segs[k].dst, segs[k].len};
+  FetchArgs A{d_src, nullptr, f->segs_dev, (uint32_t)nsegs, total};
   HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
-  A.segs = f->segs_dev;
-  A.nsegs = (uint32_t)nsegs;
-  A.total = total;
   const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
-  HIP_TRY(hipEventRecord(f->ev[0], f->st));
-  fetch_kernel<<<grid, 256, 0, f->st>>>(A);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(f->ev[1], f->st));
-  HIP_TRY(hipEventSynchronize(f->ev[1]));  // (a default event: the kernel's host writes are visible)
-  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
-  return TSG_OK;
+  return fetch_run(f, ms, [&]() -> int {
+    fetch_kernel<<<grid, 256, 0, f->st>>>(A);
+    HIP_TRY(hipGetLastError());
+    return TSG_OK;
+  });
 }
 
 int gate_spans(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, const uint64_t* starts_dev,
                const uint64_t* lengths_dev, uint8_t* flags_dev, uint32_t nfiles, float* ms) {
   *ms = 0;
   if (!nfiles) return TSG_OK;
-  std::lock_guard<std::mutex> g(f->m);
-  HIP_TRY(hipSetDevice(f->d->device));
+  FetchCall call(f);
+  if (call.rc) return call.rc;
   SpanGateArgs A{d_base, base_bytes, starts_dev, lengths_dev, flags_dev, nfiles};
   const int grid = (int)std::min<uint64_t>(((uint64_t)nfiles + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
-  HIP_TRY(hipEventRecord(f->ev[0], f->st));
-  binary_gate_kernel<<<grid, 256, 0, f->st>>>(A);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(f->ev[1], f->st));
-  HIP_TRY(hipEventSynchronize(f->ev[1]));  // (a default event: the flags are visible to the host)
-  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
-  return TSG_OK;
+  return fetch_run(f, ms, [&]() -> int {
+    binary_gate_kernel<<<grid, 256, 0, f->st>>>(A);
+    HIP_TRY(hipGetLastError());
+    return TSG_OK;
+  });
 }
 
 int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uint8_t* host_dst, uint64_t dst_bytes,
@@ -4209,8 +4231,8 @@ int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uin
     if (segs[k].src > base_bytes || segs[k].len > base_bytes - segs[k].src || segs[k].dst > dst_bytes ||
         segs[k].len > dst_bytes - segs[k].dst)
       return fail(TSG_ERR_INTERNAL, "fetch segment outside its buffers");
-  std::lock_guard<std::mutex> g(f->m);
-  HIP_TRY(hipSetDevice(f->d->device));
+  FetchCall call(f);
+  if (call.rc) return call.rc;
   if (f->gsegs_cap < nsegs) {
     if (f->gsegs) HIP_TRY(hipHostFree(f->gsegs));
     f->gsegs = nullptr;
@@ -4221,29 +4243,22 @@ int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uin
     f->gsegs_cap = cap;
   }
   std::memcpy(f->gsegs, segs, sizeof(GatherSeg) * nsegs);
-  GatherArgs A{};
-  A.src = d_base;
-  A.src_bytes = base_bytes;
+  GatherArgs A{d_base, base_bytes, nullptr, dst_bytes, f->gsegs_dev, (uint32_t)nsegs};
   HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
-  A.dst_bytes = dst_bytes;
-  A.segs = f->gsegs_dev;
-  A.nsegs = (uint32_t)nsegs;
   const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
-  HIP_TRY(hipEventRecord(f->ev[0], f->st));
-  gather_kernel<false><<<grid, 256, 0, f->st>>>(A);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(f->ev[1], f->st));
-  HIP_TRY(hipEventSynchronize(f->ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
-  return TSG_OK;
+  return fetch_run(f, ms, [&]() -> int {
+    gather_kernel<false><<<grid, 256, 0, f->st>>>(A);
+    HIP_TRY(hipGetLastError());
+    return TSG_OK;
+  });
 }
 
 int mark_tar(DeviceFetch* f, const uint8_t* d_tar, uint64_t tar_len, uint64_t* marks, float* ms) {
   *ms = 0;
   const uint64_t nblocks = tar_len / 512, words = (nblocks + 63) / 64;
   if (!words) return TSG_OK;
-  std::lock_guard<std::mutex> g(f->m);
-  HIP_TRY(hipSetDevice(f->d->device));
+  FetchCall call(f);
+  if (call.rc) return call.rc;
   if (f->marks_cap < 2 * words) {
     if (f->marks) HIP_TRY(hipFree(f->marks));
     f->marks = nullptr;
@@ -4255,28 +4270,31 @@ int mark_tar(DeviceFetch* f, const uint8_t* d_tar, uint64_t tar_len, uint64_t* m
   TarMarkArgs A{d_tar, tar_len, f->marks, f->marks + words, nblocks, words};
   // a wave per bitmap word, four per workgroup; past 8 workgroups per CU the grid strides
   const int grid = (int)std::min<uint64_t>((words + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
-  HIP_TRY(hipEventRecord(f->ev[0], f->st));
-  tar_mark_kernel<<<grid, 256, 0, f->st>>>(A);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(f->ev[1], f->st));
-  // both bitmaps in one D2H (they lie back to back)
-  HIP_TRY(hipMemcpyAsync(marks, f->marks, sizeof(uint64_t) * 2 * words, hipMemcpyDeviceToHost, f->st));
+  const int rc = fetch_run(
+      f, ms,
+      [&]() -> int {
+        tar_mark_kernel<<<grid, 256, 0, f->st>>>(A);
+        HIP_TRY(hipGetLastError());
+        return TSG_OK;
+      },
+      [&]() -> int {  // untimed: both bitmaps in one D2H (they lie back to back)
+        HIP_TRY(hipMemcpyAsync(marks, f->marks, sizeof(uint64_t) * 2 * words, hipMemcpyDeviceToHost, f->st));
+        return TSG_OK;
+      });
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(f->st));
-  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
   return TSG_OK;
 }
 
 int fetch_whole(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t* host_dst, float* ms) {
   *ms = 0;
   if (!total) return TSG_OK;
-  std::lock_guard<std::mutex> g(f->m);
-  HIP_TRY(hipSetDevice(f->d->device));
-  HIP_TRY(hipEventRecord(f->ev[0], f->st));
-  HIP_TRY(hipMemcpyAsync(host_dst, d_src, total, hipMemcpyDeviceToHost, f->st));
-  HIP_TRY(hipEventRecord(f->ev[1], f->st));
-  HIP_TRY(hipEventSynchronize(f->ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
-  return TSG_OK;
+  FetchCall call(f);
+  if (call.rc) return call.rc;
+  return fetch_run(f, ms, [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(host_dst, d_src, total, hipMemcpyDeviceToHost, f->st));
+    return TSG_OK;
+  });
 }
 
 }  // namespace tsg
