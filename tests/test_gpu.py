@@ -342,6 +342,26 @@ def test_pipelined_batches_gpu(builtin):
     assert st["batches"] == 4 and st["sum_k1_ms"] > 0 and st["sum_h2d_ms"] > 0
 
 
+def test_lane_buffers_grow_shrink_grow_gpu(builtin):
+    """Each lane sees a small batch, a larger one, a smaller one and a larger one still: its
+    HBM buffers grow, are kept over the smaller batch and grow again.  The batches go in
+    pairs, so one lane frees and reallocates while the other is busy.  Every batch == the
+    exact CPU path over the same batch."""
+    sizes = [64 << 10, 64 << 10, 1 << 20, 1 << 20, 256 << 10, 256 << 10, 4 << 20, 4 << 20]
+    batches = [corpus.make_corpus(n, seed=70 + k, plants_per_mib=60)[0] for k, n in enumerate(sizes)]
+    ctx = S.GpuContext(builtin, 0)
+    got = []
+    for k in range(0, len(batches), 2):
+        for b in batches[k:k + 2]:
+            ctx.upload(b)
+            ctx.submit()
+        got += [ctx.collect() for _ in batches[k:k + 2]]
+    st = ctx.stats()
+    ctx.close()
+    assert got == [builtin.ScanBatch(b, nthreads=16) for b in batches]
+    assert st["batches"] == 8
+
+
 def test_zero_copy_slots_gpu(builtin):
     b, _ = corpus.make_corpus(16 << 20, seed=45, plants_per_mib=20)
     ctx = S.GpuContext(builtin, 0)

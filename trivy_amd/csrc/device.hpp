@@ -2,15 +2,21 @@
 //
 // One DeviceRules per device holds the compiled rule set's tables in HBM (K1 literal
 // automaton, K2 rule-group DFAs, the Global.AllowPath DFA, gates).  A batch runs on one
-// DeviceLane (its own HIP stream and HBM buffers); enqueue_scan puts the whole device part
-// of a batch on that stream with no host round trip:
+// LaneState (its own HIP stream and HBM buffers, each an owning DevBuf grown on demand);
+// enqueue_scan computes the batch's shape once (BatchShape), reserves the lane's buffers and
+// puts the whole device part of the batch on that stream with no host round trip, stage by
+// stage with a BatchEvent recorded before each:
 //
-//   H2D (pinned slot -> HBM; for a device-resident batch stage_kernel, caller's HBM -> lane
-//   buffer, or gather_kernel for files given as spans of the caller's buffer) and one H2D of
-//   the file offsets  prep (zero fills, coarse file map)  K1  keyword gates  event-chunk
-//   compaction  item counts  item layout (device-side)  item lists  K2  outputs (candidates,
-//   keyword bits, overflow / skip flags, counters: written straight into pinned, host-mapped
-//   memory)
+//   input     the content by the batch's ScanSource (H2D from the pinned slot; stage_kernel,
+//             caller's HBM -> lane buffer; gather_kernel for files given as spans of the
+//             caller's buffer) and one H2D of the file offsets
+//   prep      zero fills, coarse file map
+//   K1        K1F or the keyword automaton (each adapts once), then K1X
+//   gates     keyword gates and event-chunk compaction, item counts, item layout
+//             (device-side), item lists
+//   K2        list pass, dense pass
+//   outputs   candidates, keyword bits, overflow / skip flags, counters: written straight
+//             into pinned, host-mapped memory
 //
 // and records the batch's completion event.  Two lanes per device let the H2D of one batch
 // overlap the kernels of the other.  The files of a device-resident batch that the host
@@ -30,6 +36,13 @@ namespace tsg {
 
 struct DeviceRules;
 
+// Stage boundaries of a batch on its lane's stream (HostOut::ev), each named for the stage
+// that starts there: the content into the lane buffer (H2D, stage_kernel or gather_kernel) |
+// the file offsets' H2D | prep | the wait for the previous batch's kernels (the other
+// lane's) | K1 | gates and the item passes | K2 | outputs.  enqueue_scan records them in this
+// order and batch_times reads the span from each to the next; kEvDone completes the batch.
+enum BatchEvent : int { kEvH2D = 0, kEvMeta, kEvPrep, kEvWait, kEvK1, kEvGates, kEvK2, kEvOut, kEvDone };
+
 // Pinned host memory of one batch's device outputs, which the outputs kernel writes straight
 // into host-mapped memory (no runtime D2H copy).
 struct HostOut {
@@ -43,13 +56,8 @@ struct HostOut {
   uint32_t* counts = nullptr;   // [kCounts] the batch's counter block (CountSlot)
   uint32_t files_cap = 0, cand_cap = 0, groups = 0, kw_words = 0;
   uint32_t wall_khz = 0;        // the device wall clock's rate (hipDeviceAttributeWallClockRate)
-  // stage boundaries of the batch on its lane's stream: data H2D | offsets H2D | prep |
-  // wait for the previous batch's kernels | K1 | gates | K2 | outputs; ev[kEvDone]
-  // completes the batch
-  hipEvent_t ev[9] = {};
+  hipEvent_t ev[kEvDone + 1] = {};  // the batch's stage boundaries (BatchEvent)
 };
-
-constexpr int kEvDone = 8;
 
 // The per-batch counter block: u32 slots in HBM (LaneState::counts; prep zeroes them, the
 // kernels count into them) which the outputs kernel copies whole to HostOut::counts.  This
@@ -97,29 +105,35 @@ struct GatherSeg {
   uint64_t src, dst, len;
 };
 
+// Where a batch's content comes from.  The offsets always come from pinned host memory.
+enum class ScanSource {
+  kHostSlot,   // pinned host: one H2D (two when the slot has no room behind the batch)
+  kPackedHbm,  // the packed batch in the caller's HBM (tsg_device_submit): stage_kernel
+  kHbmSpans,   // files as spans of the caller's HBM buffer (tsg_device_spans_submit): gather_kernel
+};
+
 struct ScanInput {
-  const uint8_t* data;       // pinned host, `total` bytes
-  const uint64_t* off;       // [nfiles + 1]
+  ScanSource kind;
+  const uint64_t* off;       // [nfiles + 1], pinned host
   uint32_t nfiles;
   uint64_t total;
-  const char* paths;         // pinned host
-  const uint64_t* poff;      // [nfiles + 1]
-  // the slot's whole pinned data buffer (data == room): enqueue_scan writes the zero tail
-  // and a copy of the offsets behind the batch there, so one H2D carries all three
+  // kHostSlot: `total` bytes of pinned host memory.  `room` is the slot's whole pinned data
+  // buffer (data == room), or null: enqueue_scan writes the zero tail and a copy of the
+  // offsets behind the batch there, so one H2D carries all three
+  const uint8_t* data = nullptr;
   uint8_t* room = nullptr;
   uint64_t room_bytes = 0;
-  // a device-resident batch (tsg_device_submit): `total` bytes in the caller's HBM at any
-  // byte alignment, staged into the lane buffer by stage_kernel instead of the content H2D
-  // (data is then null: the pinned slot holds no content until the batch's fetch)
+  // kPackedHbm: `total` bytes in the caller's HBM at any byte alignment, staged into the lane
+  // buffer by stage_kernel instead of the content H2D (the pinned slot holds no content
+  // until the batch's fetch).  kHbmSpans: the caller's buffer of src_bytes bytes
   const uint8_t* dev_src = nullptr;
-  // spans of a device buffer (tsg_device_spans_submit): dev_src is the caller's buffer of
-  // src_bytes bytes and gather_kernel copies these segments of it into the lane buffer in
-  // the stage's place.  `gather` is non-null for every such batch (ngather may be 0) and
-  // lies in pinned memory that outlives the batch's kernels; gather_dev is its device address.
+  uint64_t src_bytes = 0;
+  // kHbmSpans: gather_kernel copies these segments of dev_src into the lane buffer in the
+  // stage's place (ngather may be 0).  They lie in pinned memory that outlives the batch's
+  // kernels; gather_dev is its device address.
   const GatherSeg* gather = nullptr;
   const GatherSeg* gather_dev = nullptr;
   uint32_t ngather = 0;
-  uint64_t src_bytes = 0;
 };
 
 // pinned bytes a slot's data buffer keeps past its capacity for that tail and the offsets

@@ -2818,8 +2818,9 @@ __global__ void __launch_bounds__(kBlock) k2_dense_kernel(const DevDFA* __restri
 }
 
 // ---------------------------------------------------------------- host side
-template <class T>
-static int upload_vec(const std::vector<T>& v, const T** dst, std::vector<void*>* allocs) {
+// (P is T or const T: the kernels' argument structs hold const pointers, DeviceRules its own)
+template <class T, class P>
+static int upload_vec(const std::vector<T>& v, P** dst, std::vector<void*>* allocs) {
   void* p = nullptr;
   // whole 16-B units, zero padded: the kernels stage tables with 16-B loads (stage16)
   const size_t bytes = (std::max<size_t>(v.size() * sizeof(T), 16) + 15) & ~(size_t)15;
@@ -2827,7 +2828,7 @@ static int upload_vec(const std::vector<T>& v, const T** dst, std::vector<void*>
   HIP_TRY(hipMemset(p, 0, bytes));
   if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   allocs->push_back(p);
-  *dst = (const T*)p;
+  *dst = (T*)p;
   return TSG_OK;
 }
 
@@ -3127,6 +3128,32 @@ static int make_device_k1(const Plan& p, DevK1* out, std::vector<void*>* allocs,
   return TSG_OK;
 }
 
+// One device buffer and its capacity in elements: freed with its owner, never copied.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p); }
+  operator T*() const { return p; }
+  // Room for n elements.  A buffer that has it stays; otherwise it is freed (hipFree waits for
+  // the device) and allocated again: an eighth more than asked, in whole 16-B units, or, with
+  // `exact`, n elements as they are.  After a failed allocation the buffer is empty, so the
+  // next call allocates again.
+  int ensure(size_t n, bool exact = false) {
+    if (cap >= n && p) return TSG_OK;
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    const size_t alloc = exact ? n : std::max<size_t>(n + n / 8, 16);
+    HIP_TRY(hipMalloc((void**)&p, exact ? alloc * sizeof(T) : (alloc * sizeof(T) + 15) & ~(size_t)15));
+    cap = alloc;
+    return TSG_OK;
+  }
+};
+
 // ---------------------------------------------------------------- rule tables on a device
 struct DeviceRules {
   uint32_t all_kw_rows = 0;  // the plan has host-only rules: the host reads every keyword row
@@ -3148,8 +3175,8 @@ struct DeviceRules {
   uint32_t k1f_maxlen = 4;  // longest K1F literal (its event list's zone)
   DevK1F k1f{};
   K1FTables k1ft;        // host copy (the adaptation rebuilds it)
-  uint32_t* d_fhits = nullptr;  // [n_lit] K1F sampling counters
-  uint32_t* d_hits = nullptr;
+  DevBuf<uint32_t> d_fhits;  // [n_lit] K1F sampling counters
+  DevBuf<uint32_t> d_hits;   // [k1.ns] the automaton's
   bool adapted = false;
   uint32_t hot_states = 0;
   std::shared_ptr<const std::vector<uint8_t>> kw_unknown;
@@ -3170,8 +3197,6 @@ struct DeviceRules {
     (void)hipSetDevice(device);
     if (kernels_done) (void)hipEventDestroy(kernels_done);
     for (auto* p : tables) (void)hipFree(p);
-    (void)hipFree(d_hits);
-    (void)hipFree(d_fhits);
   }
 };
 
@@ -3179,70 +3204,42 @@ struct DeviceRules {
 struct LaneState {
   DeviceRules* d = nullptr;
   hipStream_t st = nullptr;
-  uint8_t* data_alloc = nullptr;  // kPad | batch | tail
-  size_t data_cap = 0;
-  uint8_t* meta = nullptr;        // the batch's file offsets (one H2D per batch)
-  size_t meta_cap = 0;
+  DevBuf<uint8_t> data_alloc;  // kPad | batch | tail
+  DevBuf<uint8_t> meta;        // the batch's file offsets (one H2D per batch)
   const uint64_t* off = nullptr;  // into meta (last batch)
-  uint32_t* cf = nullptr;         // coarse file map (file_of)
-  size_t cf_cap = 0;
-  uint32_t* ev_bits = nullptr;
-  size_t ev_cap = 0;
-  uint2* xlist = nullptr;  // K1X hit records
-  size_t xlist_cap = 0;
-  uint32_t* xcount = nullptr;  // K1X records per block
-  size_t xcount_cap = 0;
-  uint32_t* evlist = nullptr;
-  size_t evlist_cap = 0;
-  uint32_t* zclaim = nullptr;  // K1F's zone claims (K1FArgs::claim): a bit per chunk
-  size_t zclaim_cap = 0;
-  unsigned long long* wtrace = nullptr;  // K1F's per-wave trace (TSG_K1F_TRACE)
-  size_t wtrace_cap = 0, wtrace_n = 0;
-  uint32_t* kw = nullptr;
-  size_t kw_cap = 0;
-  unsigned long long* ggate = nullptr;
-  size_t ggate_cap = 0;
-  uint8_t* ovf = nullptr;
-  size_t ovf_cap = 0;
-  uint8_t* hascand = nullptr;
-  size_t hascand_cap = 0;
-  uint2* items = nullptr;
-  size_t items_cap = 0;
-  uint4* entries = nullptr;
-  size_t entries_cap = 0;
-  uint4* dentries = nullptr;
-  size_t dentries_cap = 0;
-  DevCand* cand = nullptr;
-  uint32_t cand_cap = 0;
-  uint32_t* counts = nullptr;   // [kCounts] the batch's counter block (CountSlot, device.hpp)
-  uint32_t* gcount = nullptr;   // [G]
-  uint32_t* bcount = nullptr;   // [grid * G] items_count_kernel's per-block counts
-  uint32_t* cursor = nullptr;   // [G]
-  uint8_t* gskip = nullptr;     // [G]
-  unsigned long long* etrace = nullptr;  // [entries_cap * kTraceW] K2 entry trace (TSG_K2_TRACE)
-  size_t etrace_cap = 0;
+  DevBuf<uint32_t> cf;         // coarse file map (file_of)
+  DevBuf<uint32_t> ev_bits;
+  DevBuf<uint2> xlist;         // K1X hit records
+  DevBuf<uint32_t> xcount;     // K1X records per block
+  DevBuf<uint32_t> evlist;
+  DevBuf<uint32_t> zclaim;     // K1F's zone claims (K1FArgs::claim): a bit per chunk
+  DevBuf<unsigned long long> wtrace;  // K1F's per-wave trace (TSG_K1F_TRACE)
+  size_t wtrace_n = 0;
+  DevBuf<uint32_t> kw;
+  DevBuf<unsigned long long> ggate;
+  DevBuf<uint8_t> ovf;
+  DevBuf<uint8_t> hascand;
+  DevBuf<uint2> items;
+  DevBuf<uint4> entries;
+  DevBuf<uint4> dentries;
+  DevBuf<DevCand> cand;        // [HostOut::cand_cap]
+  DevBuf<uint32_t> counts;     // [kCounts] the batch's counter block (CountSlot, device.hpp)
+  DevBuf<uint32_t> gcount;     // [G]
+  DevBuf<uint32_t> bcount;     // [grid * G] items_count_kernel's per-block counts
+  DevBuf<uint32_t> cursor;     // [G]
+  DevBuf<uint8_t> gskip;       // [G]
+  DevBuf<unsigned long long> etrace;  // [entries_cap * kTraceW] K2 entry trace (TSG_K2_TRACE)
   uint64_t nchunks = 0;         // last batch
+  uint8_t* data() const { return data_alloc.p + kPad; }  // the batch in the lane buffer
+  // the device is current and the stream drained before the buffers free themselves (the
+  // members' destructors run after this body)
   ~LaneState() {
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (st) (void)hipStreamSynchronize(st);
-    void* bufs[] = {data_alloc, meta, cf, ev_bits, xlist, xcount, evlist, zclaim, wtrace, kw, ggate, ovf, hascand,
-                    items, entries, dentries, cand, counts, gcount, bcount, cursor, gskip, etrace};
-    for (void* b : bufs) (void)hipFree(b);
     if (st) (void)hipStreamDestroy(st);
   }
 };
-
-template <class T>
-static int ensure(T** p, size_t* cap, size_t n) {
-  if (*cap >= n && *p) return TSG_OK;
-  if (*p) HIP_TRY(hipFree(*p));  // (hipFree waits for the device)
-  *p = nullptr;
-  const size_t alloc = std::max<size_t>(n + n / 8, 16);
-  HIP_TRY(hipMalloc((void**)p, (alloc * sizeof(T) + 15) & ~(size_t)15));
-  *cap = alloc;
-  return TSG_OK;
-}
 
 template <bool PACKED, int LDSK, bool REP, int TPB>
 static const void* k1_fn_w(uint32_t kw_words) {
@@ -3282,8 +3279,29 @@ static int launch_k1(DeviceRules* r, const K1Args& A, hipStream_t st) {
   void* args[] = {&d, &a};
   HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(threads), args, 0, st));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipGetLastError());
   return TSG_OK;
+}
+
+// What both adaptations silence: of the ids with hits in the sample, the hottest first, until
+// the rest arrive at most once per 4 KiB of it.  exact(id): the id must keep reporting.
+template <class Exact>
+static std::vector<uint32_t> hottest_over_budget(const std::vector<uint32_t>& hits, uint64_t sample_bytes, Exact exact) {
+  uint64_t tot = 0;
+  std::vector<uint32_t> order, drop;
+  for (uint32_t i = 0; i < hits.size(); i++)
+    if (hits[i]) {
+      tot += hits[i];
+      order.push_back(i);
+    }
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hits[a] > hits[b]; });
+  const uint64_t budget = sample_bytes / 4096;  // reporting budget: one arrival per 4 KiB
+  for (uint32_t i : order) {
+    if (tot <= budget) break;
+    if (exact(i)) continue;
+    drop.push_back(i);
+    tot -= hits[i];
+  }
+  return drop;
 }
 
 // K1 adaptation (once per device, on the first large batch): a sampling pass counts the
@@ -3301,7 +3319,7 @@ static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfile
   const uint64_t step = std::max<uint64_t>(1, k1_items / 16384);
   const uint64_t nsamp = (k1_items + step - 1) / step;
   HIP_TRY(hipMemsetAsync(r->d_hits, 0, sizeof(uint32_t) * ns, l->st));
-  K1Args A{l->data_alloc + kPad, l->off, l->cf, total, nchunks, nsamp, step, r->chunk,
+  K1Args A{l->data(), l->off, l->cf, total, nchunks, nsamp, step, r->chunk,
            nfiles, l->kw, l->ev_bits, r->d_hits, (uint32_t)kK1Seg};
   int rc;
   if ((rc = launch_k1(r, A, l->st))) return rc;
@@ -3310,27 +3328,19 @@ static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfile
   HIP_TRY(hipStreamSynchronize(l->st));
   r->adapted = true;
   const uint64_t sample_bytes = nsamp * kK1Chains * A.seg * r->chunk;
-  uint64_t tot = 0;
-  std::vector<uint32_t> order;
-  for (uint32_t s = 0; s < ns; s++)
-    if (hits[s]) {
-      tot += hits[s];
-      order.push_back(s);
-    }
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hits[a] > hits[b]; });
-  const uint64_t budget = sample_bytes / 4096;  // reporting budget: one arrival per 4 KiB
   std::vector<uint8_t> hot(p.kw_dfa->nstates, 0);  // automaton states that stop reporting
   auto kw_unknown = std::make_shared<std::vector<uint8_t>>(p.n_kw, 0);
   uint32_t ev_hot = 0, nhot = 0;
-  for (uint32_t s : order) {  // s: device state id
-    if (tot <= budget) break;
-    const uint32_t* m = r->k1h.masks.data() + (size_t)r->k1h.accs[s] * mw;
-    bool fallback = false;  // folding-rune literals must stay exact (they force host resolution)
-    for (int k = p.fb_kw0; k < p.n_kw; k++) fallback |= (m[k / 32] >> (k % 32)) & 1;
-    if (fallback) continue;
+  auto mask_of = [&](uint32_t s) { return r->k1h.masks.data() + (size_t)r->k1h.accs[s] * mw; };  // s: device state id
+  auto folds = [&](uint32_t s) {  // folding-rune literals must stay exact (they force host resolution)
+    bool fallback = false;
+    for (int k = p.fb_kw0; k < p.n_kw; k++) fallback |= (mask_of(s)[k / 32] >> (k % 32)) & 1;
+    return fallback;
+  };
+  for (uint32_t s : hottest_over_budget(hits, sample_bytes, folds)) {
+    const uint32_t* m = mask_of(s);
     hot[r->k1h.order[s]] = 1;
     nhot++;
-    tot -= hits[s];
     for (int k = 0; k < p.n_kw; k++)
       if ((m[k / 32] >> (k % 32)) & 1) (*kw_unknown)[k] = 1;
     ev_hot |= m[W];
@@ -3444,25 +3454,14 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
   r->adapted = true;
   const uint64_t sample_bytes = std::min<uint64_t>((uint64_t)A.ntiles * kFTile, A.total);
   const K1FLit* recs = (const K1FLit*)(r->k1ft.img.data() + kFImgLits);
-  std::vector<uint32_t> order;
-  uint64_t tot = 0;
-  for (uint32_t i = 0; i < nrec; i++)
-    if (hits[i]) {
-      tot += hits[i];
-      order.push_back(i);
-    }
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hits[a] > hits[b]; });
-  const uint64_t budget = sample_bytes / 4096;  // reporting budget: one arrival per 4 KiB
   std::vector<uint8_t> quiet(p.n_lit, 0);
   auto kw_unknown = std::make_shared<std::vector<uint8_t>>(p.n_kw, 0);
   uint32_t ev_hot = 0, nhot = 0;
-  for (uint32_t i : order) {
-    if (tot <= budget) break;
+  auto folds = [&](uint32_t i) { return (int)recs[i].id >= p.fb_kw0 && (int)recs[i].id < p.n_kw; };  // folding runes stay exact
+  for (uint32_t i : hottest_over_budget(hits, sample_bytes, folds)) {
     const uint32_t id = recs[i].id;
-    if ((int)id >= p.fb_kw0 && (int)id < p.n_kw) continue;  // folding runes stay exact
     quiet[id] = 1;
     nhot++;
-    tot -= hits[i];
     if ((int)id < p.n_kw) (*kw_unknown)[id] = 1;
     ev_hot |= p.lit_event[id];
   }
@@ -3520,7 +3519,7 @@ int device_rules_create(int device, const Plan& p, uint32_t chunk, uint32_t ext_
     r->k1f.img = (const uint8_t*)img;
     r->k1f.kw_words = (uint32_t)p.kw_words;
     if ((rc = upload_k1f(r.get()))) return rc;
-    HIP_TRY(hipMalloc((void**)&r->d_fhits, sizeof(uint32_t) * std::max(1, p.n_lit)));
+    if ((rc = r->d_fhits.ensure(std::max(1, p.n_lit), true))) return rc;
     r->use_k1f = true;
   }
   for (uint8_t h : p.rule_hostonly) r->all_kw_rows |= h;
@@ -3530,7 +3529,7 @@ int device_rules_create(int device, const Plan& p, uint32_t chunk, uint32_t ext_
   if (r->has_k1x && r->k1x.img_bytes <= kXImgLds)
     HIP_TRY(hipFuncSetAttribute((const void*)k1x_verify_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 r->k1x.img_bytes));
-  HIP_TRY(hipMalloc((void**)&r->d_hits, sizeof(uint32_t) * r->k1.ns));
+  if ((rc = r->d_hits.ensure(r->k1.ns, true))) return rc;
   const uint32_t G = (uint32_t)p.groups.size();
   if (G > 0x7FFF) return fail(TSG_ERR_INTERNAL, "more K2 groups than transition records can name");
   r->GW = std::max<uint32_t>(1, (G + 63) / 64);
@@ -3567,17 +3566,11 @@ int device_rules_create(int device, const Plan& p, uint32_t chunk, uint32_t ext_
     HIP_TRY(hipFuncSetAttribute((const void*)k2_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)r->max_lds));
   }
-  const uint32_t* cg = nullptr;
-  if ((rc = upload_vec(gmask, &cg, &r->tables))) return rc;
-  r->d_gmask = (uint32_t*)cg;
-  if ((rc = upload_vec(galways, &cg, &r->tables))) return rc;
-  r->d_galways = (uint32_t*)cg;
-  if ((rc = upload_vec(gevents, &cg, &r->tables))) return rc;
-  r->d_gevents = (uint32_t*)cg;
-  if ((rc = upload_vec(r->gback, &cg, &r->tables))) return rc;
-  r->d_gback = (uint32_t*)cg;
-  const unsigned long long* cb = nullptr;
-  if ((rc = upload_vec(gofbit, &cb, &r->tables))) return rc;
+  if ((rc = upload_vec(gmask, &r->d_gmask, &r->tables))) return rc;
+  if ((rc = upload_vec(galways, &r->d_galways, &r->tables))) return rc;
+  if ((rc = upload_vec(gevents, &r->d_gevents, &r->tables))) return rc;
+  if ((rc = upload_vec(r->gback, &r->d_gback, &r->tables))) return rc;
+  if ((rc = upload_vec(gofbit, &r->d_gofbit, &r->tables))) return rc;
   {  // the gate kernel's tables: keyword -> groups, always-gated groups as bits
     const uint32_t nkw = (uint32_t)p.kw_words * 32;
     std::vector<unsigned long long> kwg((size_t)nkw * r->GW, 0), galw(r->GW, 0);
@@ -3586,19 +3579,13 @@ int device_rules_create(int device, const Plan& p, uint32_t chunk, uint32_t ext_
         if ((gmask[(size_t)g * p.kw_words + k / 32] >> (k % 32)) & 1) kwg[(size_t)k * r->GW + g / 64] |= 1ull << (g % 64);
       if (galways[g]) galw[g / 64] |= 1ull << (g % 64);
     }
-    const unsigned long long* c64 = nullptr;
-    if ((rc = upload_vec(kwg, &c64, &r->tables))) return rc;
-    r->d_kwg = (unsigned long long*)c64;
-    if ((rc = upload_vec(galw, &c64, &r->tables))) return rc;
-    r->d_galw = (unsigned long long*)c64;
+    if ((rc = upload_vec(kwg, &r->d_kwg, &r->tables))) return rc;
+    if ((rc = upload_vec(galw, &r->d_galw, &r->tables))) return rc;
   }
   r->h_galways = galways;
   r->h_gevents = gevents;
   r->h_gofbit = gofbit;
-  r->d_gofbit = (unsigned long long*)cb;
-  const DevDFA* cd = nullptr;
-  if ((rc = upload_vec(r->groups, &cd, &r->tables))) return rc;
-  r->d_groups = (DevDFA*)cd;
+  if ((rc = upload_vec(r->groups, &r->d_groups, &r->tables))) return rc;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   r->cus = prop.multiProcessorCount;
@@ -3634,11 +3621,12 @@ int lane_create(DeviceRules* d, LaneState** out) {
   l->d = d;
   HIP_TRY(hipStreamCreateWithFlags(&l->st, hipStreamNonBlocking));
   const uint32_t G = std::max<uint32_t>(1, (uint32_t)d->groups.size());
-  HIP_TRY(hipMalloc((void**)&l->counts, sizeof(uint32_t) * kCounts));
-  HIP_TRY(hipMalloc((void**)&l->gcount, sizeof(uint32_t) * G));
-  HIP_TRY(hipMalloc((void**)&l->bcount, sizeof(uint32_t) * G * (size_t)d->grid));
-  HIP_TRY(hipMalloc((void**)&l->cursor, sizeof(uint32_t) * G));
-  HIP_TRY(hipMalloc((void**)&l->gskip, G));
+  int rc;  // (fixed sizes: allocated as they are)
+  if ((rc = l->counts.ensure(kCounts, true))) return rc;
+  if ((rc = l->gcount.ensure(G, true))) return rc;
+  if ((rc = l->bcount.ensure(G * (size_t)d->grid, true))) return rc;
+  if ((rc = l->cursor.ensure(G, true))) return rc;
+  if ((rc = l->gskip.ensure(G, true))) return rc;
   *out = l.release();
   return TSG_OK;
 }
@@ -3699,112 +3687,141 @@ int host_out_alloc(const DeviceRules* d, uint32_t files_cap, uint32_t cand_cap, 
   return TSG_OK;
 }
 
-int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out) {
-  const Plan& p = *r->plan;
-  HIP_TRY(hipSetDevice(r->device));
-  const uint32_t W = (uint32_t)p.kw_words;
-  const uint32_t C = r->chunk;
-  const uint32_t F = in.nfiles;
-  const uint64_t total = in.total;
-  const uint32_t G = (uint32_t)r->groups.size();
-  hipStream_t st = l->st;
-  if (F > out->files_cap) return fail(TSG_ERR_ARG, "batch has more files than its output buffers");
+// What enqueue_scan derives from a batch before it touches the device: sizes, capacities and
+// the paths the batch takes.  Filled once (batch_shape), read by every stage.
+struct BatchShape {
+  uint32_t W, C, F, G;  // keyword words, chunk bytes, files, rule groups
+  uint64_t total, nchunks, nchunks_pad, ncf;
+  size_t tail, o_off, meta_bytes;  // zero tail; [batch | tail] in whole 16-B units; the offsets' bytes
+  bool one_copy;  // the slot has room behind the batch: [batch | zero tail | offsets] in one H2D
+  bool k1f;       // K1 runs as K1F
+  uint64_t k1_items;
+  uint32_t k1f_tiles;
+  // item capacity and dense budget (internal.hpp): over them, groups are skipped
+  // (kGroupSkip) and resolved on the host, never dropped
+  uint64_t items_cap;
+  uint32_t max_dense;
+  uint64_t entries_cap, dentries_cap, zclaim_words;
+  bool work;           // the gates, the item passes and K2 have something to do
+  uint32_t kwg_bytes;  // the keyword -> groups table (DeviceRules::d_kwg)
+};
+
+static int batch_shape(const DeviceRules* r, const ScanInput& in, const HostOut* out, BatchShape* s) {
+  const uint32_t C = s->C = r->chunk;
+  const uint64_t total = s->total = in.total;
+  s->W = (uint32_t)r->plan->kw_words;
+  s->F = in.nfiles;
+  s->G = (uint32_t)r->groups.size();
+  if (s->F > out->files_cap) return fail(TSG_ERR_ARG, "batch has more files than its output buffers");
   if (total / C >= (1ull << 32) - 2) return fail(TSG_ERR_ARG, "batch too large for u32 chunk ids");
-  for (uint32_t k = 0; in.gather && k < in.ngather; k++) {  // nothing outside either buffer
+  const bool spans = in.kind == ScanSource::kHbmSpans;
+  for (uint32_t k = 0; spans && k < in.ngather; k++) {  // nothing outside either buffer
     const GatherSeg& g = in.gather[k];
     if (g.src > in.src_bytes || g.len > in.src_bytes - g.src || g.dst > total || g.len > total - g.dst)
       return fail(TSG_ERR_INTERNAL, "gather segment outside its buffers");
   }
-  if (in.gather && in.ngather && (!in.dev_src || !in.gather_dev))
-    return fail(TSG_ERR_INTERNAL, "gather without a source");
-  const uint64_t nchunks = (total + C - 1) / C;
-  l->nchunks = nchunks;
+  if (spans && in.ngather && (!in.dev_src || !in.gather_dev)) return fail(TSG_ERR_INTERNAL, "gather without a source");
+  s->nchunks = (total + C - 1) / C;
   // K1F addresses the batch with 32-bit offsets (and its tiles past the end)
-  const bool k1f = r->use_k1f && total + (1u << 16) < (1ull << 32);
-  int rc;
-  // ---- buffers (grown on demand; growing waits for the device)
+  s->k1f = r->use_k1f && total + (1u << 16) < (1ull << 32);
   // (K1F reads whole 1 KiB tiles, kFDepth past its last: at least 8 KiB of zero tail)
-  const size_t tail = std::max<size_t>((size_t)kK1Chains * kK1Seg * C + kPad, 8192);
-  const size_t meta_bytes = sizeof(uint64_t) * ((size_t)F + 1);
-  // one H2D when the slot has room behind the batch: [batch | zero tail | offsets]
-  const size_t o_off = ((size_t)total + tail + 15) & ~(size_t)15;
-  const bool one_copy = in.room == in.data && in.room_bytes >= o_off + meta_bytes;
-  if ((rc = ensure(&l->data_alloc, &l->data_cap, kPad + o_off + meta_bytes))) return rc;
-  uint8_t* data = l->data_alloc + kPad;
-  if (one_copy) {
-    l->off = (const uint64_t*)(data + o_off);
-  } else {
-    if ((rc = ensure(&l->meta, &l->meta_cap, meta_bytes))) return rc;
-    l->off = (const uint64_t*)l->meta;
-  }
+  s->tail = std::max<size_t>((size_t)kK1Chains * kK1Seg * C + kPad, 8192);
+  s->meta_bytes = sizeof(uint64_t) * ((size_t)s->F + 1);
+  s->o_off = ((size_t)total + s->tail + 15) & ~(size_t)15;
+  s->one_copy = in.kind == ScanSource::kHostSlot && in.room == in.data && in.room_bytes >= s->o_off + s->meta_bytes;
   const uint64_t k1_item_chunks = (uint64_t)kK1Chains * kK1Seg;
-  const uint64_t nchunks_pad = (nchunks + k1_item_chunks - 1) / k1_item_chunks * k1_item_chunks + 1;
-  const uint64_t ncf = (total >> kCfShift) + 2;
-  if ((rc = ensure(&l->cf, &l->cf_cap, (size_t)ncf))) return rc;
-  if ((rc = ensure(&l->ev_bits, &l->ev_cap, (size_t)nchunks_pad + 4))) return rc;
-  // K1X hit records: one per 256 bytes (a lane-word with a hit past that verifies inline)
-  if (r->has_k1x && (rc = ensure(&l->xlist, &l->xlist_cap, (size_t)(total / 256 + 65536)))) return rc;
-  if (r->has_k1x && (rc = ensure(&l->xcount, &l->xcount_cap, (size_t)std::max(r->cus, 1)))) return rc;
-  if ((rc = ensure(&l->evlist, &l->evlist_cap, (size_t)nchunks_pad))) return rc;
-  const uint64_t zclaim_words = nchunks_pad / 32 + 2;
-  if (k1f && (rc = ensure(&l->zclaim, &l->zclaim_cap, (size_t)zclaim_words))) return rc;
-  if ((rc = ensure(&l->kw, &l->kw_cap, (size_t)F * W + 1))) return rc;
-  if ((rc = ensure(&l->ggate, &l->ggate_cap, (size_t)F * r->GW + 1))) return rc;
-  if ((rc = ensure(&l->ovf, &l->ovf_cap, (size_t)F + 1))) return rc;
-  if ((rc = ensure(&l->hascand, &l->hascand_cap, (size_t)F + 1))) return rc;
-  // item capacity and dense budget (internal.hpp): over them, groups are skipped
-  // (kGroupSkip) and resolved on the host, never dropped
-  const uint64_t items_cap = k2_items_cap(nchunks);
-  const uint32_t max_dense = k2_max_dense();
-  const uint64_t entries_cap = items_cap / kEntryItems + G + 1;
-  const uint64_t dentries_cap = (uint64_t)max_dense * ((nchunks + kEntryChunks - 1) / kEntryChunks + 1);
-  if ((rc = ensure(&l->items, &l->items_cap, (size_t)items_cap))) return rc;
-  if ((rc = ensure(&l->entries, &l->entries_cap, (size_t)entries_cap))) return rc;
-  if ((rc = ensure(&l->dentries, &l->dentries_cap, (size_t)dentries_cap))) return rc;
-  if (!l->cand || l->cand_cap < out->cand_cap) {
-    if (l->cand) HIP_TRY(hipFree(l->cand));
-    HIP_TRY(hipMalloc((void**)&l->cand, sizeof(DevCand) * (size_t)out->cand_cap));
-    l->cand_cap = out->cand_cap;
+  s->k1_items = (s->nchunks + k1_item_chunks - 1) / k1_item_chunks;
+  s->nchunks_pad = s->k1_items * k1_item_chunks + 1;
+  s->ncf = (total >> kCfShift) + 2;
+  s->k1f_tiles = (uint32_t)((total + kFTile - 1) / kFTile);
+  s->zclaim_words = s->nchunks_pad / 32 + 2;
+  s->items_cap = k2_items_cap(s->nchunks);
+  s->max_dense = k2_max_dense();
+  s->entries_cap = s->items_cap / kEntryItems + s->G + 1;
+  s->dentries_cap = (uint64_t)s->max_dense * ((s->nchunks + kEntryChunks - 1) / kEntryChunks + 1);
+  s->work = s->F && s->G && s->nchunks;
+  s->kwg_bytes = (uint32_t)(32ull * s->W * r->GW * 8);
+  return TSG_OK;
+}
+
+int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out) {
+  const Plan& p = *r->plan;
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = l->st;
+  BatchShape s;
+  int rc;
+  if ((rc = batch_shape(r, in, out, &s))) return rc;
+  const uint64_t total = s.total;
+  l->nchunks = s.nchunks;
+  // ---- buffers (grown on demand; growing waits for the device)
+  if ((rc = l->data_alloc.ensure(kPad + s.o_off + s.meta_bytes))) return rc;
+  uint8_t* data = l->data();
+  if (s.one_copy) {
+    l->off = (const uint64_t*)(data + s.o_off);
+  } else {
+    if ((rc = l->meta.ensure(s.meta_bytes))) return rc;
+    l->off = (const uint64_t*)l->meta.p;
   }
-  // ---- H2D from the pinned slot: the batch, its zero tail and its file offsets in one
+  if ((rc = l->cf.ensure((size_t)s.ncf))) return rc;
+  if ((rc = l->ev_bits.ensure((size_t)s.nchunks_pad + 4))) return rc;
+  // K1X hit records: one per 256 bytes (a lane-word with a hit past that verifies inline)
+  if (r->has_k1x && (rc = l->xlist.ensure((size_t)(total / 256 + 65536)))) return rc;
+  if (r->has_k1x && (rc = l->xcount.ensure((size_t)std::max(r->cus, 1)))) return rc;
+  if ((rc = l->evlist.ensure((size_t)s.nchunks_pad))) return rc;
+  if (s.k1f && (rc = l->zclaim.ensure((size_t)s.zclaim_words))) return rc;
+  if ((rc = l->kw.ensure((size_t)s.F * s.W + 1))) return rc;
+  if ((rc = l->ggate.ensure((size_t)s.F * r->GW + 1))) return rc;
+  if ((rc = l->ovf.ensure((size_t)s.F + 1))) return rc;
+  if ((rc = l->hascand.ensure((size_t)s.F + 1))) return rc;
+  if ((rc = l->items.ensure((size_t)s.items_cap))) return rc;
+  if ((rc = l->entries.ensure((size_t)s.entries_cap))) return rc;
+  if ((rc = l->dentries.ensure((size_t)s.dentries_cap))) return rc;
+  if ((rc = l->cand.ensure(out->cand_cap, true))) return rc;
+  // ---- input.  From the pinned slot: the batch, its zero tail and its file offsets in one
   // runtime copy (the paths stay on the host, where Global.AllowPath is settled per file,
   // scanner.go:343-347); a buffer without room behind the batch takes a second copy
-  HIP_TRY(hipEventRecord(out->ev[0], st));
-  if (one_copy) {
-    std::memset(in.room + total, 0, o_off - total);
-    std::memcpy(in.room + o_off, in.off, meta_bytes);
-    HIP_TRY(hipMemcpyAsync(data, in.room, o_off + meta_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(out->ev[1], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvH2D], st));
+  if (s.one_copy) {
+    std::memset(in.room + total, 0, s.o_off - total);
+    std::memcpy(in.room + s.o_off, in.off, s.meta_bytes);
+    HIP_TRY(hipMemcpyAsync(data, in.room, s.o_off + s.meta_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(out->ev[kEvMeta], st));
   } else {
-    if (in.gather) {
-      // spans of the caller's buffer: the kept files back to back into the lane buffer, in
-      // the stage's place and under its events (no launch for a batch without bytes)
-      if (in.ngather) {
-        GatherArgs GA{in.dev_src, in.src_bytes, data, total, in.gather_dev, in.ngather};
-        const int ggrid = (int)std::min<uint64_t>(in.ngather, (uint64_t)std::max(r->grid, 1));
-        gather_kernel<true><<<ggrid, 256, 0, st>>>(GA);
-        HIP_TRY(hipGetLastError());
-      }
-    } else if (total && in.dev_src) {
-      // device-resident batch: HBM -> HBM on this lane's stream (one read and one write of the
-      // batch; ev[0]..ev[1], the H2D's place, times it)
-      const uint64_t words = (total + 15) / 16;
-      const int sgrid = (int)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)r->grid));
-      stage_kernel<<<sgrid, 256, 0, st>>>(data, in.dev_src, total);
-      HIP_TRY(hipGetLastError());
-    } else if (total) {
-      HIP_TRY(hipMemcpyAsync(data, in.data, total, hipMemcpyHostToDevice, st));
+    switch (in.kind) {
+      case ScanSource::kHbmSpans:
+        // spans of the caller's buffer: the kept files back to back into the lane buffer, in
+        // the stage's place and under its events (no launch for a batch without bytes)
+        if (in.ngather) {
+          GatherArgs GA{in.dev_src, in.src_bytes, data, total, in.gather_dev, in.ngather};
+          const int ggrid = (int)std::min<uint64_t>(in.ngather, (uint64_t)std::max(r->grid, 1));
+          gather_kernel<true><<<ggrid, 256, 0, st>>>(GA);
+          HIP_TRY(hipGetLastError());
+        }
+        break;
+      case ScanSource::kPackedHbm:
+        // device-resident batch: HBM -> HBM on this lane's stream (one read and one write of the
+        // batch; kEvH2D..kEvMeta, the H2D's place, times it)
+        if (total) {
+          const uint64_t words = (total + 15) / 16;
+          const int sgrid = (int)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)r->grid));
+          stage_kernel<<<sgrid, 256, 0, st>>>(data, in.dev_src, total);
+          HIP_TRY(hipGetLastError());
+        }
+        break;
+      case ScanSource::kHostSlot:
+        if (total) HIP_TRY(hipMemcpyAsync(data, in.data, total, hipMemcpyHostToDevice, st));
+        break;
     }
-    HIP_TRY(hipEventRecord(out->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(l->meta, in.off, meta_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(out->ev[kEvMeta], st));
+    HIP_TRY(hipMemcpyAsync(l->meta, in.off, s.meta_bytes, hipMemcpyHostToDevice, st));
   }
-  HIP_TRY(hipEventRecord(out->ev[2], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvPrep], st));
   // ---- prep: zero fills and the coarse file map, one kernel
   {
     PrepArgs PA{};
     PA.off = l->off;
-    PA.nfiles = F;
-    PA.ncf = F ? ncf : 0;
+    PA.nfiles = s.F;
+    PA.ncf = s.F ? s.ncf : 0;
     PA.cf = l->cf;
     bool too_many = false;
     auto zero = [&](void* ptr, uint64_t n) {
@@ -3817,18 +3834,19 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
       PA.zn[PA.nz++] = n;
     };
     zero(l->data_alloc, kPad);
-    if (!one_copy) zero(data + total, tail);
-    zero(l->kw, sizeof(uint32_t) * (uint64_t)F * W);
-    zero(l->ovf, F);
-    zero(l->hascand, F);
+    if (!s.one_copy) zero(data + total, s.tail);
+    zero(l->kw, sizeof(uint32_t) * (uint64_t)s.F * s.W);
+    zero(l->ovf, s.F);
+    zero(l->hascand, s.F);
     zero(l->counts, sizeof(uint32_t) * kCounts);
-    if (k1f) zero(l->ev_bits, sizeof(uint32_t) * nchunks_pad);  // K1F ORs events in
-    if (k1f) zero(l->zclaim, sizeof(uint32_t) * zclaim_words);    // K1F's zone claims
-    zero(l->gcount, sizeof(uint32_t) * G);
-    zero(l->cursor, sizeof(uint32_t) * G);
-    zero(l->gskip, G);
+    if (s.k1f) zero(l->ev_bits, sizeof(uint32_t) * s.nchunks_pad);  // K1F ORs events in
+    if (s.k1f) zero(l->zclaim, sizeof(uint32_t) * s.zclaim_words);    // K1F's zone claims
+    zero(l->gcount, sizeof(uint32_t) * s.G);
+    zero(l->cursor, sizeof(uint32_t) * s.G);
+    zero(l->gskip, s.G);
     if (too_many) return fail(TSG_ERR_INTERNAL, "more zero fills than the prep kernel takes");
-    const uint64_t work = std::max<uint64_t>({PA.ncf, (uint64_t)F * W / 4, one_copy ? 1 : tail / 16, k1f ? nchunks_pad / 4 : 1, 1});
+    const uint64_t work = std::max<uint64_t>(
+        {PA.ncf, (uint64_t)s.F * s.W / 4, s.one_copy ? 1 : s.tail / 16, s.k1f ? s.nchunks_pad / 4 : 1, 1});
     const int pgrid = (int)std::min<uint64_t>((work + 255) / 256, (uint64_t)r->grid);
     prep_kernel<<<pgrid, 256, 0, st>>>(PA);
     HIP_TRY(hipGetLastError());
@@ -3837,54 +3855,53 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   // their HIP-event times are the kernels' own), while this lane's H2D and prep above
   // overlapped the previous batch's kernels on the other lane (prep touches this lane's
   // buffers only: off the critical path, 17 us per batch with its event)
-  HIP_TRY(hipEventRecord(out->ev[3], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvWait], st));
   if (r->kernels_done_valid) HIP_TRY(hipStreamWaitEvent(st, r->kernels_done, 0));
-  HIP_TRY(hipEventRecord(out->ev[4], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvK1], st));
 
   // ---- K1
-  const uint64_t k1_items = (nchunks + k1_item_chunks - 1) / k1_item_chunks;
   const uint64_t adapt_bytes = r->adapt_mib == 0xFFFFFFFFu ? ~0ull : (uint64_t)(r->adapt_mib ? r->adapt_mib : 16) << 20;
-  const uint32_t k1f_tiles = (uint32_t)((total + kFTile - 1) / kFTile);
   // K1F lists the event chunks itself: no compaction pass, and the item passes gate files
   // from their keyword bits (no gates pass at all)
   // (K1X, when a plan has it, adds events after K1: the gates pass lists them all)
   // (opt-in, knob k1f_list: kernel-only on the configs[1] batch it cost K1F ~3 us and the
   // item passes ~5 us more than the gates pass it replaces, profiles/r06/d)
-  const bool k1f_list = k1f && total && !r->has_k1x && knobs().k1f_list.load() && k1f_lists(r, k1f_tiles, C);
-  if (k1f) {
-    K1FArgs A{data, l->off, l->cf, (uint32_t)total, C, F, k1f_tiles, F ? (uint32_t)ncf : 0u,
+  const bool k1f_list = s.k1f && total && !r->has_k1x && knobs().k1f_list.load() && k1f_lists(r, s.k1f_tiles, s.C);
+  if (s.k1f) {
+    K1FArgs A{data, l->off, l->cf, (uint32_t)total, s.C, s.F, s.k1f_tiles, s.F ? (uint32_t)s.ncf : 0u,
               l->kw, l->ev_bits, nullptr, l->counts + kCntK1F, (unsigned long long*)(l->counts + kCntClk),
               nullptr, nullptr, r->k1f_maxlen, 0, nullptr, nullptr};
-    // (a device-resident batch has no host bytes yet: the sample comes from the staged lane buffer)
-    if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.dev_src ? nullptr : in.data))) return rc;
+    // (in.data is null unless the batch came from the pinned slot: a device-resident batch has no
+    // host bytes yet, and the sample comes from the staged lane buffer)
+    if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.data))) return rc;
     if (k1f_list) {
       A.evlist = l->evlist;
       A.nev = l->counts + kCntEvChunks;
-      A.evcap = (uint32_t)std::min<size_t>(l->evlist_cap, 0xFFFFFFFFu);
+      A.evcap = (uint32_t)std::min<size_t>(l->evlist.cap, 0xFFFFFFFFu);
       A.zone = r->k1f_maxlen;  // (after the adaptation's rebuild)
       A.claim = l->zclaim;
     }
     static const bool wtrace = getenv("TSG_K1F_TRACE") != nullptr;
     if (wtrace && total) {
-      const size_t nw = (size_t)k1f_grid(r, k1f_tiles) * (kFThreads / 64);
-      if ((rc = ensure(&l->wtrace, &l->wtrace_cap, 4 * nw))) return rc;
+      const size_t nw = (size_t)k1f_grid(r, s.k1f_tiles) * (kFThreads / 64);
+      if ((rc = l->wtrace.ensure(4 * nw))) return rc;
       HIP_TRY(hipMemsetAsync(l->wtrace, 0, sizeof(unsigned long long) * 4 * nw, st));
       A.wtrace = l->wtrace;
       l->wtrace_n = 4 * nw;
     }
     if (total && (rc = launch_k1f(r, A, st))) return rc;
-  } else if (!r->adapted && k1_items >= 64 && total >= adapt_bytes) {
-    if ((rc = adapt_k1(r, l, total, F, nchunks, k1_items))) return rc;
+  } else if (!r->adapted && s.k1_items >= 64 && total >= adapt_bytes) {
+    if ((rc = adapt_k1(r, l, total, s.F, s.nchunks, s.k1_items))) return rc;
   }
-  if (!k1f && k1_items) {
-    K1Args A{data, l->off, l->cf, total, nchunks, k1_items, 1, C, F, l->kw, l->ev_bits, nullptr, (uint32_t)kK1Seg};
+  if (!s.k1f && s.k1_items) {
+    K1Args A{data, l->off, l->cf, total, s.nchunks, s.k1_items, 1, s.C, s.F, l->kw, l->ev_bits, nullptr, (uint32_t)kK1Seg};
     if ((rc = launch_k1(r, A, st))) return rc;
   }
   if (r->has_k1x && total) {  // the hashed literals of a large rule set, after K1's stores
     const int xg = (int)std::max<uint64_t>(1, std::min<uint64_t>((total / 16 + kK1XBlock - 1) / kK1XBlock,
                                                                    (uint64_t)r->cus));
-    K1XArgs X{data, l->off, l->cf, total, C, F, l->kw, l->ev_bits, l->xlist, l->xcount,
-              (uint32_t)std::min<size_t>(l->xlist_cap, 0xFFFFFFFFu), l->counts + kCntK1X};
+    K1XArgs X{data, l->off, l->cf, total, s.C, s.F, l->kw, l->ev_bits, l->xlist, l->xcount,
+              (uint32_t)std::min<size_t>(l->xlist.cap, 0xFFFFFFFFu), l->counts + kCntK1X};
     void* xa[] = {(void*)&r->k1x, (void*)&X};
     HIP_TRY(hipLaunchKernel(k1x_fn(r->k1x.step), dim3(xg), dim3(kK1XBlock), xa, kXDwords * 4 + 16, st));
     if (r->k1x.img_bytes <= kXImgLds)
@@ -3893,7 +3910,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
       k1x_verify_kernel<false><<<xg, kXVerifyBlock, 0, st>>>(r->k1x, X, (uint32_t)xg);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(out->ev[5], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvGates], st));
 
   // ---- gates, items, device-side layout
   ItemArgs IA{};
@@ -3904,63 +3921,60 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   IA.gofbit = r->d_gofbit;
   IA.gevents = r->d_gevents;
   IA.gback = r->d_gback;
-  IA.nchunks = nchunks;
-  IA.F = F;
-  IA.G = G;
+  IA.nchunks = s.nchunks;
+  IA.F = s.F;
+  IA.G = s.G;
   IA.GW = r->GW;
-  IA.chunk = C;
+  IA.chunk = s.C;
   IA.maxback = r->maxback;
   IA.count = l->gcount;
   IA.bcount = l->bcount;
   IA.cursor = l->cursor;
   IA.evlist = l->evlist;
   IA.nev = l->counts + kCntEvChunks;
-  IA.evcap = (uint32_t)std::min<size_t>(l->evlist_cap, 0xFFFFFFFFu);
+  IA.evcap = (uint32_t)std::min<size_t>(l->evlist.cap, 0xFFFFFFFFu);
   IA.items = l->items;
   IA.kw = l->kw;
-  IA.W = W;
+  IA.W = s.W;
   IA.kwg = r->d_kwg;
   IA.galw = r->d_galw;
   IA.clk = (unsigned long long*)(l->counts + kCntClk);
-  const bool work = F && G && nchunks;
-  if (work && k1f_list) {
+  if (s.work && k1f_list) {
     IA.ggate = nullptr;  // (files gated from their keyword bits in the item passes)
-  } else if (work) {
-    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((nchunks + kEvPer * kBlock - 1) / (kEvPer * kBlock), (uint64_t)r->grid);
-    const uint32_t kwg_bytes = (uint32_t)(32ull * W * r->GW * 8);
-    GateArgs GA{l->ev_bits, nchunks, l->evlist, l->counts + kCntEvChunks, cgrid, l->kw, F, W, r->GW, r->d_kwg, r->d_galw, l->ggate,
-                (unsigned long long*)(l->counts + kCntClk), kwg_bytes <= kKwgLdsMax ? kwg_bytes : 0u};
-    gates_kernel<<<cgrid + (F + kBlock - 1) / kBlock, kBlock, GA.kwg_lds, st>>>(GA);
+  } else if (s.work) {
+    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((s.nchunks + kEvPer * kBlock - 1) / (kEvPer * kBlock), (uint64_t)r->grid);
+    GateArgs GA{l->ev_bits, s.nchunks, l->evlist, l->counts + kCntEvChunks, cgrid, l->kw, s.F, s.W, r->GW, r->d_kwg, r->d_galw, l->ggate,
+                (unsigned long long*)(l->counts + kCntClk), s.kwg_bytes <= kKwgLdsMax ? s.kwg_bytes : 0u};
+    gates_kernel<<<cgrid + (s.F + kBlock - 1) / kBlock, kBlock, GA.kwg_lds, st>>>(GA);
     HIP_TRY(hipGetLastError());
   }
-  if (work) {
+  if (s.work) {
     // both items passes (bcount holds grid x G); kItemsBpc blocks per CU
     const int igrid = std::min(r->grid, r->cus * kItemsBpc);
-    const uint32_t kwg_bytes = (uint32_t)(32ull * W * r->GW * 8);
-    IA.kwg_lds = !IA.ggate && kwg_bytes <= kItemKwgLdsMax ? kwg_bytes : 0u;
-    const size_t ilds = item_lds_host(G, r->GW) + IA.kwg_lds;
-    hipLaunchKernelGGL(items_count_kernel, dim3(igrid), dim3(kBlock), ilds + G * sizeof(uint32_t) + 16, st, IA);
+    IA.kwg_lds = !IA.ggate && s.kwg_bytes <= kItemKwgLdsMax ? s.kwg_bytes : 0u;
+    const size_t ilds = item_lds_host(s.G, r->GW) + IA.kwg_lds;
+    hipLaunchKernelGGL(items_count_kernel, dim3(igrid), dim3(kBlock), ilds + s.G * sizeof(uint32_t) + 16, st, IA);
     HIP_TRY(hipGetLastError());
-    LayoutArgs LA{l->gcount, G, nchunks, items_cap, max_dense, l->entries, l->counts + kCntListEntries,
+    LayoutArgs LA{l->gcount, s.G, s.nchunks, s.items_cap, s.max_dense, l->entries, l->counts + kCntListEntries,
                   l->dentries, l->counts + kCntDenseEntries, l->gskip, l->counts + kCntLayout};
-    hipLaunchKernelGGL(items_emit_kernel, dim3(igrid), dim3(kBlock), ilds + 3 * G * sizeof(uint32_t) + G + 16, st, IA, LA);
+    hipLaunchKernelGGL(items_emit_kernel, dim3(igrid), dim3(kBlock), ilds + 3 * s.G * sizeof(uint32_t) + s.G + 16, st, IA, LA);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(out->ev[6], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvK2], st));
 
   // ---- K2 over the work list
-  if (work) {
+  if (s.work) {
     K2Args A{};
     A.data = data;
     A.off = l->off;
     A.cf = l->cf;
     A.total = total;
-    A.nchunks = nchunks;
-    A.chunk = C;
+    A.nchunks = s.nchunks;
+    A.chunk = s.C;
     A.ext_cap = r->ext_cap;
-    A.nfiles = F;
+    A.nfiles = s.F;
     A.kw = l->kw;
-    A.kw_words = W;
+    A.kw_words = s.W;
     A.gmask = r->d_gmask;
     A.galways = r->d_galways;
     A.items = l->items;
@@ -3976,11 +3990,11 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     static const bool diag = getenv("TSG_K2_DIAG") != nullptr;
     A.diag = diag ? l->counts + kCntK2Diag : nullptr;
     A.claim = l->counts + kCntK2Claim;
-    A.word_recs = G <= 0x3FFF && !knobs().k2_no_word_recs.load();
+    A.word_recs = s.G <= 0x3FFF && !knobs().k2_no_word_recs.load();
     static const bool trace = getenv("TSG_K2_TRACE") != nullptr;
-    if (trace && (rc = ensure(&l->etrace, &l->etrace_cap, (size_t)entries_cap * kTraceW))) return rc;
-    if (trace) HIP_TRY(hipMemsetAsync(l->etrace, 0, sizeof(unsigned long long) * entries_cap * kTraceW, st));
-    A.etrace = trace ? l->etrace : nullptr;
+    if (trace && (rc = l->etrace.ensure((size_t)s.entries_cap * kTraceW))) return rc;
+    if (trace) HIP_TRY(hipMemsetAsync(l->etrace, 0, sizeof(unsigned long long) * s.entries_cap * kTraceW, st));
+    A.etrace = trace ? l->etrace.p : nullptr;
     A.clk = (unsigned long long*)(l->counts + kCntClk);
     // one block per resident slot (the grids are persistent)
     if (r->k2_rich)
@@ -3994,7 +4008,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     // (the dense pass on a second stream beside the list pass: K2 0.125 -> 0.152 ms per
     // batch, the two grids slowed each other; profiles/r04/e)
   }
-  HIP_TRY(hipEventRecord(out->ev[7], st));
+  HIP_TRY(hipEventRecord(out->ev[kEvOut], st));
   HIP_TRY(hipEventRecord(r->kernels_done, st));
   r->kernels_done_valid = true;
 
@@ -4003,7 +4017,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     OutArgs OA{};
     OA.count = l->counts;
     OA.cand_cap = out->cand_cap;
-    OA.cand = (const uint8_t*)l->cand;
+    OA.cand = (const uint8_t*)l->cand.p;
     OA.cand_host = (uint8_t*)out->cand_dev;
     auto copy = [&](void* host, const void* dev, uint64_t n) {
       if (n) {
@@ -4013,14 +4027,14 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
       }
     };
     copy(out->counts, l->counts, sizeof(uint32_t) * kCounts);
-    copy(out->gskip, l->gskip, G);
+    copy(out->gskip, l->gskip, s.G);
     OA.kw = l->kw;
     OA.kw_host = (uint32_t*)(out->blk_dev + ((uint8_t*)out->kw - out->blk));
     OA.ovf = l->ovf;
     OA.hascand = l->hascand;
     OA.flags_host = out->blk_dev + (out->ovf - out->blk);
-    OA.F = F;
-    OA.W = W;
+    OA.F = s.F;
+    OA.W = s.W;
     OA.fb_lo = (uint32_t)p.fb_kw0;
     OA.fb_hi = (uint32_t)p.n_kw;
     OA.all_rows = r->all_kw_rows;
@@ -4032,16 +4046,15 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
 }
 
 int batch_times(const HostOut* o, ScanTimes* t) {
-  float x[kEvDone] = {};
-  for (int k = 0; k < kEvDone; k++) HIP_TRY(hipEventElapsedTime(&x[k], o->ev[k], o->ev[k + 1]));
-  t->h2d = x[0];
-  t->meta = x[1];
-  t->prep = x[2];  // (prep runs before the wait on the other lane's kernels)
-  t->wait = x[3];
-  t->k1 = x[4];
-  t->gates = x[5];
-  t->k2 = x[6];
-  t->out = x[7];
+  auto between = [&](BatchEvent a, BatchEvent b, float* ms) { return hipEventElapsedTime(ms, o->ev[a], o->ev[b]); };
+  HIP_TRY(between(kEvH2D, kEvMeta, &t->h2d));
+  HIP_TRY(between(kEvMeta, kEvPrep, &t->meta));
+  HIP_TRY(between(kEvPrep, kEvWait, &t->prep));  // (prep runs before the wait on the other lane's kernels)
+  HIP_TRY(between(kEvWait, kEvK1, &t->wait));
+  HIP_TRY(between(kEvK1, kEvGates, &t->k1));
+  HIP_TRY(between(kEvGates, kEvK2, &t->gates));
+  HIP_TRY(between(kEvK2, kEvOut, &t->k2));
+  HIP_TRY(between(kEvOut, kEvDone, &t->out));
   // the kernels' own spans by the device wall clock (ClkStamp; 0 if a kernel did not run;
   // a start is stored as its complement)
   const unsigned long long* c = (const unsigned long long*)(o->counts + kCntClk);
@@ -4053,44 +4066,47 @@ int batch_times(const HostOut* o, ScanTimes* t) {
   return TSG_OK;
 }
 
-int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out) {
+// the test hooks below read a lane at rest: its device current, its stream drained
+static int lane_sync(LaneState* l) {
   HIP_TRY(hipSetDevice(l->d->device));
   HIP_TRY(hipStreamSynchronize(l->st));
+  return TSG_OK;
+}
+
+int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out) {
+  if (int rc = lane_sync(l)) return rc;
   out->clear();
   if (!l->etrace) return TSG_OK;
   uint32_t nent = 0;
   HIP_TRY(hipMemcpy(&nent, l->counts + kCntListEntries, sizeof(nent), hipMemcpyDeviceToHost));
-  const size_t n = std::min<size_t>((size_t)nent * kTraceW, l->etrace_cap);
+  const size_t n = std::min<size_t>((size_t)nent * kTraceW, l->etrace.cap);
   out->resize(n);
   if (n) HIP_TRY(hipMemcpy(out->data(), l->etrace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return TSG_OK;
 }
 
 int lane_k1f_trace(LaneState* l, std::vector<unsigned long long>* out) {
-  HIP_TRY(hipSetDevice(l->d->device));
-  HIP_TRY(hipStreamSynchronize(l->st));
+  if (int rc = lane_sync(l)) return rc;
   out->assign(l->wtrace ? l->wtrace_n : 0, 0);
   if (!out->empty()) HIP_TRY(hipMemcpy(out->data(), l->wtrace, out->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return TSG_OK;
 }
 
 int lane_kw(LaneState* l, uint32_t* kw, size_t n) {
-  HIP_TRY(hipSetDevice(l->d->device));
-  HIP_TRY(hipStreamSynchronize(l->st));
+  if (int rc = lane_sync(l)) return rc;
   if (n) HIP_TRY(hipMemcpy(kw, l->kw, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
   return TSG_OK;
 }
 
 int lane_items(LaneState* l, LaneItems* out) {
-  HIP_TRY(hipSetDevice(l->d->device));
-  HIP_TRY(hipStreamSynchronize(l->st));
+  if (int rc = lane_sync(l)) return rc;
   uint32_t nent = 0, ndent = 0, nitems = 0;
   HIP_TRY(hipMemcpy(&nent, l->counts + kCntListEntries, sizeof(nent), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&ndent, l->counts + kCntDenseEntries, sizeof(ndent), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&nitems, l->counts + kCntItems, sizeof(nitems), hipMemcpyDeviceToHost));
   // (the counters are the layout's; the buffers' own sizes bound every copy)
-  const size_t ne = std::min<size_t>(nent, l->entries_cap), nd = std::min<size_t>(ndent, l->dentries_cap),
-               ni = std::min<size_t>(nitems, l->items_cap), G = l->d->groups.size();
+  const size_t ne = std::min<size_t>(nent, l->entries.cap), nd = std::min<size_t>(ndent, l->dentries.cap),
+               ni = std::min<size_t>(nitems, l->items.cap), G = l->d->groups.size();
   out->entries.assign(4 * ne, 0);
   out->dentries.assign(4 * nd, 0);
   out->items.assign(2 * ni, 0);
@@ -4104,8 +4120,7 @@ int lane_items(LaneState* l, LaneItems* out) {
 }
 
 int lane_events(LaneState* l, uint32_t* ev, size_t n) {
-  HIP_TRY(hipSetDevice(l->d->device));
-  HIP_TRY(hipStreamSynchronize(l->st));
+  if (int rc = lane_sync(l)) return rc;
   if (n && l->nchunks)
     HIP_TRY(hipMemcpy(ev, l->ev_bits, sizeof(uint32_t) * std::min<uint64_t>(n, l->nchunks), hipMemcpyDeviceToHost));
   return TSG_OK;

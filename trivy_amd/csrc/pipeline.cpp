@@ -75,7 +75,7 @@ constexpr uint32_t kUnknownFill = 0xFFFFFFFFu;
 // ScanInput of a submission of the slot's first nfiles files (lock held)
 ScanInput slot_input(const Slot& s, uint32_t nfiles) {
   const bool room = s.inflight == 0 && s.filled == nfiles;
-  return ScanInput{s.data, s.off, nfiles, s.off[nfiles], s.paths, s.poff, room ? s.data : nullptr,
+  return ScanInput{ScanSource::kHostSlot, s.off, nfiles, s.off[nfiles], s.data, room ? s.data : nullptr,
                    room ? s.data_cap + slot_room_bytes(s.files_cap) : 0};
 }
 
@@ -632,14 +632,12 @@ int submit_locked(tsg_ctx* c, uint32_t sid, uint32_t nfiles, bool keep_result,
     LaneState* l = c->lanes[c->seq++ % c->lanes.size()];
     ScanInput in = slot_input(s, nfiles);
     if (d.on()) {  // the content comes from the caller's HBM; the slot's is fetched later
-      in.data = nullptr;
-      in.room = nullptr;
-      in.room_bytes = 0;
+      in = ScanInput{d.spans ? ScanSource::kHbmSpans : ScanSource::kPackedHbm, s.off, nfiles, s.off[nfiles]};
       in.dev_src = d.src;
-      in.gather = d.stage_segs;  // (null for a packed batch: stage_kernel)
+      in.src_bytes = d.base_bytes;
+      in.gather = d.stage_segs;  // (spans only: a packed batch goes through stage_kernel)
       in.gather_dev = d.stage_segs_dev;
       in.ngather = d.n_stage_segs;
-      in.src_bytes = d.base_bytes;
     }
     if ((rc = enqueue_scan(c->dr, l, in, &c->outs[b->out]))) {
       c->out_busy[b->out] = 0;
