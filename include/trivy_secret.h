@@ -256,6 +256,35 @@ int tsg_batch_items(tsg_ctx* ctx, uint32_t slot_id, uint32_t* entries, size_t en
 int tsg_batch_candidates(tsg_ctx* ctx, uint32_t slot_id, uint32_t* records, size_t records_cap,
                          uint8_t* flags, size_t flags_len, uint32_t* kw, size_t kw_len, uint64_t* n);
 
+/* Test hook: what the context's K1 adaptation decided (tsg_ctx_options.adapt_mib: once per
+ * context, on the first batch of that size).  Read-only and synchronous, under the context
+ * lock.  On an emulated context and before an adaptation it succeeds with adapted = 0. */
+typedef struct tsg_adaptation_info {
+  uint32_t adapted;      /* 1 once the sampling launch has run and its decision is applied */
+  uint32_t k1_filter;    /* 1 = K1 is K1F, 0 = the automaton (or an emulated context) */
+  uint32_t hot_states;   /* silenced ids: K1F literals, or accepting states of the automaton */
+  uint32_t ev_hot;       /* OR of the silenced ids' event bits */
+  uint64_t sample_bytes; /* bytes of the batch the sampling launch counted in */
+  uint32_t n_keywords;   /* length of kw_unknown (tsg_ruleset_info.n_keywords) */
+  uint32_t n_groups;     /* length of gate_open and event_everywhere */
+  uint32_t n_literals;   /* length of hits and quiet: the K1 literals after a K1F adaptation,
+                          * 0 otherwise (the automaton counts per state, not per literal) */
+  uint32_t reserved;
+} tsg_adaptation_info;
+/* Up to the given lengths are copied (any array pointer may be NULL):
+ *   kw_unknown        [n_keywords] 1 = K1 no longer reports the keyword: the vector the host
+ *                     resolver gets (zeros before an adaptation)
+ *   gate_open         [n_groups] 1 = every file passes the group's keyword gate ...
+ *   event_everywhere  [n_groups] 1 = the group listens to every chunk: both as uploaded,
+ *                     read back from the device's tables
+ *   hits              [n_literals] the sampling launch's verified arrivals per K1 literal id
+ *                     (tsg_ruleset_k1_literal), 0 for an id without a record in the filter
+ *   quiet             [n_literals] 1 = the literal left the filter */
+int tsg_test_adaptation(tsg_ctx* ctx, tsg_adaptation_info* info, uint8_t* kw_unknown,
+                        size_t kw_unknown_len, uint8_t* gate_open, size_t gate_open_len,
+                        uint8_t* event_everywhere, size_t event_everywhere_len, uint32_t* hits,
+                        size_t hits_len, uint8_t* quiet, size_t quiet_len);
+
 typedef struct tsg_stats {
   double k1_ms;          /* K1 literal automaton + run counters, last collected batch (HIP events) */
   double k2_ms;          /* K2 rule-group DFAs (the persistent work-list launch) */

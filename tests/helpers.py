@@ -735,3 +735,248 @@ def reference_output(sc, batch, chunk, ref, cand_cap=1 << 22, skipped=False):
     rows[~mark] = 0
     return {"count": len(ref), "cand_cap": cand_cap, "records": ref[:cand_cap][::-1].copy(), "flags": flags,
             "kw": rows}
+
+
+# ---------------------------------------------------------------------------------------
+# The adapted K1 (tests/test_gpu_k1_adapted.py): a batch whose hot set is known in advance,
+# the literals it makes hot chosen from the plan, and hottest_over_budget restated.
+# tests/test_k1_adapted.py checks on the CPU that the batch meets the conditions.
+
+ADAPT_TOTAL = (2 << 20) + 301                  # the whole batch is the sample at adapt_mib = 1
+ADAPT_BIG_TOTAL = (16 << 20) + (3 << 10) + 5   # past the sampling launch's 16 MiB cap
+ADAPT_HOT = 3000                               # occurrences planted per hot literal (budget: 512)
+
+
+def rule_keyword_ids(sc):
+    """Per rule the K1 literal ids of its keywords (lowercased, as the plan numbers them);
+    None for a rule whose keywords do not gate by bits (none, or one that is not ASCII)."""
+    lits = [s for s, _ in sc.k1_literals()]
+    fb0 = sc.info()["n_keywords"] - 3
+    at = {s: i for i, s in enumerate(lits[:fb0])}
+    out = []
+    for r in sc.Rules:
+        ks = [k.lower().encode() for k in r.Keywords]
+        out.append([at[k] for k in ks] if ks and all(k.isascii() and k in at for k in ks) else None)
+    return out
+
+
+def rule_events(sc):
+    """Per rule its K1 event bits (tsg_ruleset_rule_anchor)."""
+    import ctypes as C
+    from trivy_amd import _native as N
+    out = []
+    for r in range(len(sc.Rules)):
+        ev, d = C.c_uint32(), C.c_int64()
+        N.check(N.lib().tsg_ruleset_rule_anchor(sc.handle, r, C.byref(ev), C.byref(d), None, 0))
+        out.append(ev.value)
+    return out
+
+
+def adapted_picks(sc):
+    """The literals the adapted batch makes hot, chosen from the plan (Scanner.k1_literals()
+    and the rule introspection), as K1 literal ids:
+      a  a keyword without event bits, the only keyword of every rule that lists it;
+      b  an anchor literal (id >= n_keywords) with an event class;
+      c  the first folding-rune fallback literal (ids [fb_kw0, n_keywords));
+      d  a keyword of one group that is also in the event class of another group (None when
+         the rule set has none).
+    a and b hold no other literal, so planting them makes nothing else hot.  Also the rules
+    behind a (those listing it) and behind b (those of its event class)."""
+    lits = sc.k1_literals()
+    nkw = sc.info()["n_keywords"]
+    fb0 = nkw - 3
+    kws, evs = [k or [] for k in rule_keyword_ids(sc)], rule_events(sc)
+    group = [sc.rule_group(r) for r in range(len(sc.Rules))]
+
+    def plain(i):
+        return not any(j != i and s and s in lits[i][0] for j, (s, _) in enumerate(lits))
+    a = next(i for i in range(fb0) if lits[i][1] == 0 and len(lits[i][0]) >= 5 and plain(i) and
+             any(i in k for k in kws) and all(k == [i] for k in kws if i in k))
+    b = next(i for i in range(nkw, len(lits)) if lits[i][1] and plain(i))
+    d = None
+    for i in range(fb0):
+        gk = {group[r] for r in range(len(kws)) if i in kws[r] and group[r] >= 0}
+        ge = {group[r] for r in range(len(kws)) if evs[r] & lits[i][1] and not evs[r] >> 31 and group[r] >= 0}
+        if i not in (a, b) and lits[i][1] and any(g1 != g2 for g1 in gk for g2 in ge):
+            d = i
+            break
+    return {"a": a, "b": b, "c": fb0, "d": d,
+            "rules_a": [r for r in range(len(kws)) if a in kws[r]],
+            "rules_b": [r for r in range(len(kws)) if evs[r] & lits[b][1] and not evs[r] >> 31]}
+
+
+def adapted_batch(sc, total=ADAPT_TOTAL, seed=3, fold_hot=True):
+    """A batch for the K1 adaptation: files of quiet filler (helpers.quiet) of 0 bytes to
+    16 KiB, in which the literals of adapted_picks stand ADAPT_HOT times each, in random
+    letter case and at random places (the folding rune c in two files of its own: a file
+    holding one is resolved whole on the host), far over the budget of one arrival per
+    4 KiB.  Planted beside them, as corpus.make_corpus plants (a sampled secret on a line
+    of its own): in files of their own without another keyword, a secret of every rule
+    behind a and behind b; and in the other files secrets of further rules.
+
+    fold_hot = True is the batch as the adaptation's exemption must meet it: c is hot.  c
+    can never leave the filter, so the arrivals never come under the budget and every
+    literal with an occurrence is silenced (hottest_over_budget skips an exempt id without
+    taking its hits off the total); therefore only a few further rules are planted, and
+    all of their groups are touched.  fold_hot = False plants c three times and a secret
+    of every rule: a, b and d alone are silenced, and most groups with candidates stay
+    untouched.  A total above ADAPT_TOTAL repeats the files of the ADAPT_TOTAL batch and
+    ends with a filler file.  Returns (batch, picks)."""
+    import numpy as np
+    from trivy_amd import corpus
+    from trivy_amd import secret as S
+    picks = adapted_picks(sc)
+    if total > ADAPT_TOTAL:
+        base, _ = adapted_batch(sc, ADAPT_TOTAL, seed, fold_hot)
+        files = [bytes(base.data[int(base.offsets[i]):int(base.offsets[i + 1])]) for i in range(base.nfiles)]
+        reps = total // ADAPT_TOTAL
+        rng = np.random.default_rng(seed + 1)
+        args = [S.ScanArgs("r%d/%d.txt" % (k, i), c) for k in range(reps) for i, c in enumerate(files)]
+        args.append(S.ScanArgs("tail.txt", quiet(rng, total - reps * ADAPT_TOTAL)))
+        return S.Batch.from_args(args), picks
+    assert total == ADAPT_TOTAL
+    rng = np.random.default_rng(seed)
+    lits = [s for s, _ in sc.k1_literals()]
+    pool = quiet(rng, 1 << 16)
+
+    def filler(n):
+        at = int(rng.integers(0, len(pool) - n + 1))
+        return bytearray(pool[at:at + n])
+
+    def rcase(b):
+        return bytes(c - 32 if 97 <= c <= 122 and rng.random() < 0.5 else c for c in b)
+
+    def line(r):
+        return ("\n" + corpus.sample_secret(sc.Rules[r].Regex, rng) + "\n").encode()
+
+    def put(body, text):
+        at = int(rng.integers(0, len(body) - len(text) + 1))
+        body[at:at + len(text)] = text
+    # the files of their own: the folding rune, then one secret per rule behind a and b
+    own = []
+    nfold = ADAPT_HOT if fold_hot else 3
+    for k in range(2):
+        n = nfold // 2 + (nfold % 2) * k
+        own.append(bytearray(b"".join(lits[picks["c"]] + (b"\n" if i % 9 == 8 else b" ") for i in range(n))))
+    for r in picks["rules_a"] + picks["rules_b"]:
+        body = filler(600)
+        put(body, line(r))
+        own.append(body)
+    # the other files: sizes 0 .. 16 KiB, some tiny, some empty
+    left = total - sum(len(f) for f in own)
+    sizes = []
+    while left > 0:
+        k = len(sizes)
+        n = 0 if k % 11 == 5 else int(rng.integers(1, 16)) if k % 11 == 8 else int(rng.integers(64, 16 << 10))
+        sizes.append(min(n, left))
+        left -= sizes[-1]
+    rest = [filler(n) for n in sizes]
+    big = [f for f in rest if len(f) >= 256]
+    for key in ("a", "b", "d"):
+        if picks[key] is None:
+            continue
+        lit = lits[picks[key]]
+        for f in rng.integers(0, len(big), ADAPT_HOT):
+            put(big[int(f)], b" " + rcase(lit) + b" ")
+    # secrets last, over whatever stands there (the counts are taken from the final bytes)
+    rules = list(range(len(sc.Rules)))
+    planted = picks["rules_a"] + picks["rules_b"] + ([] if fold_hot else rules)
+    if fold_hot and picks["d"] is not None:
+        planted += [r for r, k in enumerate(rule_keyword_ids(sc)) if k and picks["d"] in k]
+    for r in planted * 3:
+        body = big[int(rng.integers(0, len(big)))]
+        text = line(r)
+        if len(text) <= len(body):
+            put(body, text)
+    files = [bytes(f) for f in own]
+    # the files of their own stand among the others, not at the batch's start
+    order = list(rng.permutation(len(rest)))
+    names = ["own/%d.txt" % i for i in range(len(own))]
+    out = []
+    for k, i in enumerate(order):
+        out.append(("f/%d.txt" % i, bytes(rest[int(i)])))
+        if k % 7 == 3 and files:
+            out.append((names.pop(0), files.pop(0)))
+    out += list(zip(names, files))
+    batch = S.Batch.from_args([S.ScanArgs(p, c) for p, c in out])
+    assert int(batch.offsets[-1]) == total
+    return batch, picks
+
+
+def literal_counts(sc, batch):
+    """Plain occurrence counts of every K1 literal in the batch, the definition K1F's
+    sampling counters follow (k1f_kernel's report): the batch is one byte stream with
+    ASCII letters folded to lower case; an occurrence is a position at which the
+    (lowercased) literal's bytes stand, overlapping occurrences each count, it must end
+    before the batch's last byte + 1, and file boundaries play no part."""
+    import numpy as np
+    total = int(batch.offsets[-1])
+    text = bytes(batch.data[:total]).lower()   # (bytes.lower folds ASCII letters only)
+    out = np.zeros(len(sc.k1_literals()), dtype=np.int64)
+    for i, (s, _) in enumerate(sc.k1_literals()):
+        at = text.find(s) if s else -1
+        while at >= 0:
+            out[i] += 1
+            at = text.find(s, at + 1)
+    return out
+
+
+def predict_quiet(hits, sample_bytes, exact):
+    """hottest_over_budget restated: of the ids with hits, the hottest first, drop until the
+    rest arrive at most once per 4 KiB of the sample; ids in `exact` are never dropped and
+    their hits stay in the total.  Returns (dropped ids as a set, tied): tied is True when
+    an id that stays has the hit count of the last one dropped, i.e. when the set depends
+    on the sort's order among equals."""
+    order = sorted((i for i in range(len(hits)) if hits[i]), key=lambda i: -int(hits[i]))
+    tot = sum(int(hits[i]) for i in order)
+    budget = sample_bytes // 4096
+    drop, last = set(), None
+    for i in order:
+        if tot <= budget:
+            break
+        if i in exact:
+            continue
+        drop.add(i)
+        tot -= int(hits[i])
+        last = i
+    tied = last is not None and any(
+        i not in drop and i not in exact and hits[i] == hits[last] for i in order)
+    return drop, tied
+
+
+def gates_after_adaptation(sc, kw_unknown, ev_hot):
+    """(gate_open, event_everywhere) per group, derived from the rules alone: a group's gate
+    is open when one of its rules has no keyword gate by bits (no keyword, or a non-ASCII
+    one) or lists an unknown keyword; it listens to every chunk when its rules' events hold
+    the no-anchor bit (1 << 31) or a hot event class."""
+    import numpy as np
+    G = sc.info()["n_groups"]
+    kws, evs = rule_keyword_ids(sc), rule_events(sc)
+    gate, evw = np.zeros(G, dtype=np.uint8), np.zeros(G, dtype=np.uint8)
+    for r in range(len(sc.Rules)):
+        g = sc.rule_group(r)
+        if g < 0:
+            continue
+        if kws[r] is None or any(kw_unknown[k] for k in kws[r]):
+            gate[g] = 1
+        if evs[r] >> 31 or evs[r] & ev_hot:
+            evw[g] = 1
+    return gate, evw
+def adapted_findings(sc, batch, picks, results):
+    """Of the exact findings `results` of an adapted batch: (a rule behind a has a finding in
+    a file whose only keyword bit is a, a rule behind b has a finding, the groups with
+    findings)."""
+    import numpy as np
+    ids = [r.ID for r in sc.Rules]
+    kw, _ = sc.k1_reference(batch, 256)
+    only_a = np.zeros(kw.shape[1], dtype=np.uint32)
+    only_a[picks["a"] // 32] = 1 << (picks["a"] % 32)
+    found_a = found_b = False
+    groups = set()
+    for f, r in enumerate(results):
+        for fd in r["Findings"] or []:
+            ri = ids.index(fd["RuleID"])
+            groups.add(sc.rule_group(ri))
+            found_a |= ri in picks["rules_a"] and np.array_equal(kw[f], only_a)
+            found_b |= ri in picks["rules_b"]
+    return found_a, found_b, groups

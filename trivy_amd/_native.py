@@ -91,6 +91,13 @@ class Stats(C.Structure):
                 ("k2_dense_entries", C.c_uint32), ("k2_rich", C.c_uint32)]
 
 
+class AdaptationInfo(C.Structure):
+    """tsg_adaptation_info, in the header's order."""
+    _fields_ = [("adapted", C.c_uint32), ("k1_filter", C.c_uint32), ("hot_states", C.c_uint32),
+                ("ev_hot", C.c_uint32), ("sample_bytes", C.c_uint64), ("n_keywords", C.c_uint32),
+                ("n_groups", C.c_uint32), ("n_literals", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class DeviceInputStats(C.Structure):
     """tsg_device_input_stats, in the header's order."""
     _fields_ = [("stage_ms", C.c_double), ("fetch_ms", C.c_double),
@@ -153,6 +160,8 @@ SIGNATURES = [
                                   C.c_size_t, _U8P, C.c_size_t, _U64P]),
     ("tsg_batch_candidates", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, _U8P,
                                        C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
+    ("tsg_test_adaptation", C.c_int, [_P, C.POINTER(AdaptationInfo), _U8P, C.c_size_t, _U8P, C.c_size_t,
+                                      _U8P, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U8P, C.c_size_t]),
     ("tsg_batch_collect", C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),

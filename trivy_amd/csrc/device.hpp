@@ -154,6 +154,22 @@ void device_rules_destroy(DeviceRules* d);
 // keyword bits K1 no longer reports after its adaptation (null before / without it)
 std::shared_ptr<const std::vector<uint8_t>> device_rules_kw_unknown(const DeviceRules* d);
 uint32_t device_rules_hot_states(const DeviceRules* d);
+// What the K1 adaptation decided (test hook, tsg_test_adaptation): copies, read under the
+// context lock; the gates and events are read back from HBM.  Before an adaptation: adapted
+// false, the gates and events the static ones, hits and quiet empty.  hits / quiet ([n_lit],
+// by plan literal id) exist on the K1F path only: the automaton's counters are per state,
+// not per literal.
+struct AdaptationView {
+  bool adapted = false, k1_filter = false;
+  uint32_t hot_states = 0, ev_hot = 0;
+  uint64_t sample_bytes = 0;
+  std::vector<uint8_t> kw_unknown;        // [n_kw], zeros before an adaptation
+  std::vector<uint8_t> gate_open;         // [G] d_galways
+  std::vector<uint8_t> event_everywhere;  // [G] d_gevents & kEvAlways
+  std::vector<uint32_t> hits;             // K1F: the sampling launch's counter per literal id
+  std::vector<uint8_t> quiet;             // K1F: the literals that left the filter
+};
+int device_rules_adaptation(const DeviceRules* d, AdaptationView* out);
 // true: K1 runs as K1F (k1f_kernel, batches under 4 GiB); false: the automaton (k1_kernel)
 bool device_rules_k1_filter(const DeviceRules* d);
 // true: K2's list pass runs k2_kernel_rich (decided by the occupancy API), false: k2_kernel

@@ -3179,6 +3179,13 @@ struct DeviceRules {
   DevBuf<uint32_t> d_hits;   // [k1.ns] the automaton's
   bool adapted = false;
   uint32_t hot_states = 0;
+  // what the adaptation decided (test hook device_rules_adaptation): the hot event classes,
+  // the sample's bytes, and for K1F the sampling launch's counters and the silenced
+  // literals, both by plan literal id
+  uint32_t ev_hot = 0;
+  uint64_t sample_bytes = 0;
+  std::vector<uint32_t> lit_hits;
+  std::vector<uint8_t> lit_quiet;
   std::shared_ptr<const std::vector<uint8_t>> kw_unknown;
   std::vector<uint32_t> h_galways, h_gevents;
   std::vector<unsigned long long> h_gofbit;
@@ -3346,6 +3353,8 @@ static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfile
     ev_hot |= m[W];
   }
   r->hot_states = nhot;
+  r->ev_hot = ev_hot;
+  r->sample_bytes = sample_bytes;
   if (!nhot) return TSG_OK;
   if ((rc = k1_tables(p, hot, &r->k1h, &r->k1.start, &r->k1.acc_row))) return rc;
   HIP_TRY(hipMemcpy((void*)r->k1.tab, r->k1h.tab.data(), r->k1h.tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -3434,7 +3443,8 @@ static int launch_k1f(DeviceRules* r, const K1FArgs& A, hipStream_t st) {
 // The filter is then rebuilt for the data: each window and bucket priced by its count in a
 // sample of the batch, so few words are listed for verification (profiles/r05/kv1: the
 // model-priced buckets listed 1.24 words per KiB and their verification cost 0.2 ms per GiB).
-static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint8_t* host_data) {
+static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint8_t* host_data, uint64_t kw_bytes,
+                     uint64_t ev_bytes) {
   const Plan& p = *r->plan;
   HIP_TRY(hipDeviceSynchronize());
   const uint32_t nrec = r->k1ft.nlit;
@@ -3450,6 +3460,10 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
   if ((rc = launch_k1f(r, A, l->st))) return rc;
   std::vector<uint32_t> hits(std::max<uint32_t>(1, nrec));
   HIP_TRY(hipMemcpyAsync(hits.data(), r->d_fhits, sizeof(uint32_t) * hits.size(), hipMemcpyDeviceToHost, l->st));
+  // the sampling launch ORed the old tables' bits and events into the batch's own arrays:
+  // cleared again, so that this batch's K1 output is that of the rebuilt tables alone
+  if (kw_bytes) HIP_TRY(hipMemsetAsync(l->kw, 0, kw_bytes, l->st));
+  if (ev_bytes) HIP_TRY(hipMemsetAsync(l->ev_bits, 0, ev_bytes, l->st));
   HIP_TRY(hipStreamSynchronize(l->st));
   r->adapted = true;
   const uint64_t sample_bytes = std::min<uint64_t>((uint64_t)A.ntiles * kFTile, A.total);
@@ -3466,6 +3480,12 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
     ev_hot |= p.lit_event[id];
   }
   r->hot_states = nhot;
+  r->ev_hot = ev_hot;
+  r->sample_bytes = sample_bytes;
+  r->lit_hits.assign(p.n_lit, 0);  // record index -> literal id through the tables the launch ran with
+  for (uint32_t i = 0; i < nrec; i++)
+    if ((int)recs[i].id < p.n_lit) r->lit_hits[recs[i].id] = hits[i];
+  r->lit_quiet = quiet;
   // the windows and buckets again, without the hot literals and priced by their counts in a
   // sample of the batch (16 pieces of 128 KiB spread over it: 2 MiB)
   std::vector<uint8_t> sample;
@@ -3612,6 +3632,33 @@ void device_rules_destroy(DeviceRules* d) { delete d; }
 
 std::shared_ptr<const std::vector<uint8_t>> device_rules_kw_unknown(const DeviceRules* d) { return d->kw_unknown; }
 uint32_t device_rules_hot_states(const DeviceRules* d) { return d->hot_states; }
+int device_rules_adaptation(const DeviceRules* d, AdaptationView* out) {
+  const Plan& p = *d->plan;
+  out->adapted = d->adapted;
+  out->k1_filter = d->use_k1f;
+  out->hot_states = d->hot_states;
+  out->ev_hot = d->ev_hot;
+  out->sample_bytes = d->sample_bytes;
+  if (d->kw_unknown) out->kw_unknown = *d->kw_unknown;
+  else out->kw_unknown.assign(p.n_kw, 0);
+  // the gates and events as they stand in HBM (the tables change only while the device is idle)
+  const size_t G = d->groups.size();
+  std::vector<uint32_t> ga(G), ge(G);
+  if (G) {
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipMemcpy(ga.data(), d->d_galways, sizeof(uint32_t) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ge.data(), d->d_gevents, sizeof(uint32_t) * G, hipMemcpyDeviceToHost));
+  }
+  out->gate_open.assign(G, 0);
+  out->event_everywhere.assign(G, 0);
+  for (size_t g = 0; g < G; g++) {
+    out->gate_open[g] = ga[g] ? 1 : 0;
+    out->event_everywhere[g] = (ge[g] & kEvAlways) ? 1 : 0;
+  }
+  out->hits = d->lit_hits;
+  out->quiet = d->lit_quiet;
+  return TSG_OK;
+}
 bool device_rules_k1_filter(const DeviceRules* d) { return d->use_k1f; }
 bool device_rules_k2_rich(const DeviceRules* d) { return d->k2_rich; }
 
@@ -3873,7 +3920,9 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
               nullptr, nullptr, r->k1f_maxlen, 0, nullptr, nullptr};
     // (in.data is null unless the batch came from the pinned slot: a device-resident batch has no
     // host bytes yet, and the sample comes from the staged lane buffer)
-    if (!r->adapted && total >= adapt_bytes && (rc = adapt_k1f(r, l, A, in.data))) return rc;
+    if (!r->adapted && total >= adapt_bytes &&
+        (rc = adapt_k1f(r, l, A, in.data, sizeof(uint32_t) * (uint64_t)s.F * s.W, sizeof(uint32_t) * s.nchunks_pad)))
+      return rc;
     if (k1f_list) {
       A.evlist = l->evlist;
       A.nev = l->counts + kCntEvChunks;

@@ -1488,6 +1488,45 @@ int tsg_batch_candidates(tsg_ctx* c, uint32_t slot_id, uint32_t* records, size_t
   });
 }
 
+int tsg_test_adaptation(tsg_ctx* c, tsg_adaptation_info* info, uint8_t* kw_unknown, size_t kw_unknown_len,
+                        uint8_t* gate_open, size_t gate_open_len, uint8_t* event_everywhere,
+                        size_t event_everywhere_len, uint32_t* hits, size_t hits_len, uint8_t* quiet, size_t quiet_len) {
+  if (!c || !info) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    // (the context lock: no batch is enqueued, so no adaptation runs, during the copy)
+    std::lock_guard<std::mutex> g(c->m);
+    const Plan& p = *c->rs->plan;
+    AdaptationView v;
+    if (c->emulate || !c->dr) {  // no device tables: nothing adapts
+      v.kw_unknown.assign(p.n_kw, 0);
+      for (const auto& gp : p.groups) {
+        v.gate_open.push_back(gp.always ? 1 : 0);
+        v.event_everywhere.push_back((gp.events & kEvAlways) ? 1 : 0);
+      }
+    } else if (int rc = device_rules_adaptation(c->dr, &v)) {
+      return rc;
+    }
+    std::memset(info, 0, sizeof(*info));
+    info->adapted = v.adapted;
+    info->k1_filter = v.k1_filter;
+    info->hot_states = v.hot_states;
+    info->ev_hot = v.ev_hot;
+    info->sample_bytes = v.sample_bytes;
+    info->n_keywords = (uint32_t)v.kw_unknown.size();
+    info->n_groups = (uint32_t)v.gate_open.size();
+    info->n_literals = (uint32_t)v.hits.size();
+    auto give = [](auto* dst, size_t cap, const auto& src) {
+      if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(src[0]) * std::min(cap, src.size()));
+    };
+    give(kw_unknown, kw_unknown_len, v.kw_unknown);
+    give(gate_open, gate_open_len, v.gate_open);
+    give(event_everywhere, event_everywhere_len, v.event_everywhere);
+    give(hits, hits_len, v.hits);
+    give(quiet, quiet_len, v.quiet);
+    return TSG_OK;
+  });
+}
+
 int tsg_ctx_get_stats(const tsg_ctx* c, tsg_stats* out) {
   if (!c || !out) return fail(TSG_ERR_ARG, "bad argument");
   std::lock_guard<std::mutex> g(c->m);

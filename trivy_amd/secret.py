@@ -631,6 +631,30 @@ class GpuContext:
         return {"count": int(n[0]), "cand_cap": int(n[3]), "records": rec[:n[1]],
                 "flags": flags[:b.nfiles], "kw": kw[:b.nfiles * W].reshape(b.nfiles, W)}
 
+    def adaptation(self):
+        """What the context's K1 adaptation decided (tsg_test_adaptation): {"adapted",
+        "k1_filter", "hot_states", "ev_hot", "sample_bytes", "kw_unknown": [n_keywords],
+        "gate_open": [n_groups], "event_everywhere": [n_groups], "hits": [n_literals] u32 and
+        "quiet": [n_literals] after a K1F adaptation, else None}."""
+        info = N.AdaptationInfo()
+        u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        N.check(N.lib().tsg_test_adaptation(self._h, C.byref(info), None, 0, None, 0, None, 0, None, 0, None, 0))
+        nk, ng, nl = info.n_keywords, info.n_groups, info.n_literals
+        kwu = np.zeros(max(nk, 1), dtype=np.uint8)
+        gate = np.zeros(max(ng, 1), dtype=np.uint8)
+        evw = np.zeros(max(ng, 1), dtype=np.uint8)
+        hits = np.zeros(max(nl, 1), dtype=np.uint32)
+        quiet = np.zeros(max(nl, 1), dtype=np.uint8)
+        N.check(N.lib().tsg_test_adaptation(self._h, C.byref(info), kwu.ctypes.data_as(u8p), nk,
+                                            gate.ctypes.data_as(u8p), ng, evw.ctypes.data_as(u8p), ng,
+                                            hits.ctypes.data_as(u32p), nl, quiet.ctypes.data_as(u8p), nl))
+        assert (info.n_keywords, info.n_groups, info.n_literals) == (nk, ng, nl)
+        return {"adapted": int(info.adapted), "k1_filter": int(info.k1_filter),
+                "hot_states": int(info.hot_states), "ev_hot": int(info.ev_hot),
+                "sample_bytes": int(info.sample_bytes), "kw_unknown": kwu[:nk], "gate_open": gate[:ng],
+                "event_everywhere": evw[:ng], "hits": hits[:nl] if nl else None,
+                "quiet": quiet[:nl] if nl else None}
+
     def k1_output(self, chunk):
         """(keyword bits [nfiles, kw_words], chunk event bits) of the last kernels() call."""
         assert chunk == self.chunk, "the context's chunk is %d" % self.chunk
