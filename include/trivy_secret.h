@@ -337,6 +337,9 @@ typedef struct tsg_stats {
   /* 1: K2's list pass runs k2_kernel_rich on this device, 0: k2_kernel (the occupancy API
    * decides when the context is created) */
   uint32_t k2_rich;
+  /* bytes of K1X's verify image (slot table, literal entries and bytes), 0 without K1X: up to
+   * 128 KiB k1x_verify_kernel stages it in LDS, a larger one is read from global memory */
+  uint32_t k1x_img_bytes;
 } tsg_stats;
 int tsg_ctx_get_stats(const tsg_ctx* ctx, tsg_stats* out);
 
@@ -490,7 +493,13 @@ const char* tsg_last_error(void);
  *                     sets of up to 256 rules, else 48)
  *   "k1f_grid"        cap on K1F's blocks (default: one per CU): many tiles per wave in
  *                     small test batches
- *   "k1f_list"        "1": K1F lists the chunks with events itself (no gates pass; the item
+ *   "grid_cap"        N >= 1: at most N blocks in every launch whose grid comes from the
+ *                     device or a constant (prep, stage, gather, fetch, binary gate, tar marks,
+ *                     K1, K1F, K1X and its verification, the gates pass's compaction blocks,
+ *                     both item passes, the three K2 kernels, outputs), so that a small test
+ *                     batch takes each block through many rounds of its loop; read once per
+ *                     batch or call; 0 (default): the grids as they are; negative: TSG_ERR_ARG
+ *   "k1f_list"       "1": K1F lists the chunks with events itself (no gates pass; the item
  *                     passes gate files from their keyword bits)
  *   "k2_items_cap"    K2's item capacity in the next batches (default: twice the batch's
  *                     chunks, at least 65,536); list groups past it are left to the host

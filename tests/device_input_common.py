@@ -32,9 +32,9 @@ def hostonly_case(nbytes=24 << 10):
     return sc, S.Batch.from_args(args)
 
 
-def big_file_batch():
+def big_file_batch(nsmall=24):
     """One 300 KiB file (more than four fetch segments) with a secret at its start, middle
-    and end, among small files with and without secrets and empty ones."""
+    and end, among nsmall small files with and without secrets and empty ones."""
     rng = np.random.default_rng(5)
     big = bytearray(H.quiet(rng, 300 << 10))
     for at in (0, 150 << 10, (300 << 10) - len(H.AKIA)):
@@ -42,7 +42,7 @@ def big_file_batch():
     big[len(H.AKIA)] = 10
     big[(300 << 10) - len(H.AKIA) - 1] = 10
     files = []
-    for i in range(24):
+    for i in range(nsmall):
         body = H.quiet(rng, int(rng.integers(1, 3000)))
         if i % 5 == 0:
             body = b"k = " + H.AKIA + b"\n" + body

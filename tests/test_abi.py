@@ -41,8 +41,8 @@ def test_ctypes_binding_covers_header():
 
 
 def test_stats_binding_follows_header():
-    """N.Stats lists tsg_stats' fields in the header's order, with k2_dense_entries and
-    k2_rich appended last (earlier fields keep their offsets)."""
+    """N.Stats lists tsg_stats' fields in the header's order, with k2_dense_entries, k2_rich
+    and k1x_img_bytes appended last (earlier fields keep their offsets)."""
     src = open(HEADER).read()
     body = re.search(r"typedef struct tsg_stats \{(.*?)\} tsg_stats;", src, flags=re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
@@ -52,7 +52,7 @@ def test_stats_binding_follows_header():
         words = decl.replace(",", " ").split()
         fields += [(name, ctype[words[0]]) for name in words[1:]]
     assert fields == list(N.Stats._fields_)
-    assert [n for n, _ in fields[-2:]] == ["k2_dense_entries", "k2_rich"]
+    assert [n for n, _ in fields[-3:]] == ["k2_dense_entries", "k2_rich", "k1x_img_bytes"]
 
 
 def test_config_error_and_last_error():

@@ -5,6 +5,7 @@ against the exact CPU path on larger batches.  No reference fixture covers these
 sets; the oracle is pinned by the reference fixtures (test_oracle_reference.py)."""
 import pytest
 
+from tests.gpu_common import k1_vs_reference as _k1_vs_reference
 from tests.helpers import canon_secret
 from tools.gen_oracle_fixtures import sample_expect
 from trivy_amd import analyzer as A
@@ -37,19 +38,6 @@ def test_user_rules_1000_compile(user1000):
     _, sc = user1000
     info = sc.info()
     assert info["n_rules"] == 1083 and info["n_groups"] > 0
-
-
-def _k1_vs_reference(sc, b, chunks=(64, 256)):
-    import numpy as np
-    for chunk in chunks:
-        ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, adapt_mib=0xFFFFFFFF)
-        ctx.upload(b)
-        ctx.kernels()
-        kw, ev = ctx.k1_output(chunk)
-        ctx.close()
-        rkw, rev = sc.k1_reference(b, chunk)
-        assert np.array_equal(kw, rkw)
-        assert np.array_equal(ev, rev)
 
 
 @pytest.mark.parametrize("step", [None, "1", "2", "4"])

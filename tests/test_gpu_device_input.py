@@ -127,7 +127,12 @@ def test_fetch_writes_only_its_segments(builtin, poisoned):
     """Write bounds on a batch whose fetched files start and end at every offset mod 16 and
     whose 300 KiB file is cut into several segments: after the scan the mirror holds the
     batch's bytes inside every listed segment and the untouched poison right outside each."""
-    b = big_file_batch()
+    fetch_writes_only_its_segments(builtin, big_file_batch(), 6)
+
+
+def fetch_writes_only_its_segments(builtin, b, least_segs):
+    """The comparison of test_fetch_writes_only_its_segments for a batch b (the knob
+    device_poison is on) whose fetch lists least_segs segments or more."""
     ctx = S.GpuContext(builtin, 0, adapt_mib=0xFFFFFFFF)
     try:
         want = ctx.scan_batch(b)
@@ -150,7 +155,7 @@ def test_fetch_writes_only_its_segments(builtin, poisoned):
                 hi = min(total, off + n + 32)
                 assert np.array_equal(mirror[off + n:hi], pois[off + n:hi])
                 edges += 1
-        assert edges >= 4 and len(segs) >= 6
+        assert edges >= 4 and len(segs) >= least_segs
         assert len({int(o) % 16 for o in starts}) >= 3
     finally:
         ctx.close()

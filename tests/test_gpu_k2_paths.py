@@ -4,64 +4,21 @@ dense, skip, overflow and transition-record paths through the findings of batche
 to reach them (tests/helpers.py; tests/test_k2_paths.py checks on the CPU that each input
 covers its edges).  Every comparison is exact; the references are the hooks and the exact
 CPU path."""
-import functools
-
 import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests.gpu_common import check_stats as _check_stats, dense_case as _dense_case, item_case as _item_case
+from tests.gpu_common import run_lists as _run
 from trivy_amd import corpus
 from trivy_amd import secret as S
 
 pytestmark = pytest.mark.gpu
 
-NEVER = 0xFFFFFFFF
-
 
 @pytest.fixture(scope="module")
 def builtin():
     return S.NewScanner(None)
-
-
-@functools.lru_cache(maxsize=None)
-def _scanner():
-    return S.NewScanner(None)
-
-
-@functools.lru_cache(maxsize=None)
-def _item_case(chunk, name):
-    """(batch, reference triples, counts, chunks, exact findings) of one item-pass input,
-    computed once and shared by the tests that need it."""
-    sc = _scanner()
-    batch = H.item_inputs(sc, chunk)[name]
-    tri, counts = sc.emulate_items(batch, chunk, 16)
-    return batch, tri, counts, H.nchunks_of(batch, chunk), sc.ScanBatch(batch, nthreads=16)
-
-
-@functools.lru_cache(maxsize=None)
-def _dense_case(chunk, total):
-    sc = _scanner()
-    batch, plants = H.dense_batch(chunk, total)
-    tri, counts = sc.emulate_items(batch, chunk, 16)
-    return batch, plants, tri, counts, H.nchunks_of(batch, chunk), sc.ScanBatch(batch, nthreads=16)
-
-
-def _run(sc, batch, chunk, **kw):
-    """kernels() + work lists + stats + findings of one batch on a fresh context."""
-    ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, adapt_mib=NEVER, **kw)
-    ctx.upload(batch)
-    ctx.kernels()
-    st = ctx.stats()
-    lists = ctx.batch_items()
-    got = ctx.scan()
-    st2 = ctx.stats()
-    ctx.close()
-    return lists, st, got, st2
-
-
-def _check_stats(st, tot):
-    got = (st["k2_items"], st["k2_launches"], st["k2_dense_entries"], st["groups_skipped"])
-    assert got == (tot["items"], tot["entries"], tot["dense_entries"], tot["skipped"]), (got, tot)
 
 
 @pytest.mark.parametrize("listing", ["gates", "k1f_list"])

@@ -7,89 +7,15 @@ reference stays under the default candidate capacity).  The comparison is of the
 (file, rule, end) triples as multisets, so a spurious, lost or doubled record fails here with
 its file, chunk, offset in its word, group and rule, even where the resolver's findings would
 not move.  Every comparison is exact; then scan() must equal the exact CPU path."""
-import functools
-
 import pytest
 
 from tests import helpers as H
-from trivy_amd import _native as N
-from trivy_amd import configs
-from trivy_amd import corpus
+from tests.gpu_common import k2_exact as _exact, k2_scanner_for as _scanner, run_records as _run
 from trivy_amd import secret as S
 
 pytestmark = pytest.mark.gpu
 
-NEVER = 0xFFFFFFFF
 KERNELS = ("default", "small tables")
-
-
-@functools.lru_cache(maxsize=None)
-def _scanner(rules, kernel):
-    """A scanner per rule set and list kernel: group_table_kib = 32 at compile time gives
-    smaller DFAs, for which the occupancy API picks k2_kernel instead of k2_kernel_rich."""
-    if kernel == "small tables":
-        N.knob("group_table_kib", 32)
-    try:
-        if rules == "k2":
-            return H.k2_scanner()
-        if rules == "user":
-            return S.NewScanner(S.config_from_dict(configs.user_rules_doc(1000, 4)))
-        return S.NewScanner(None)
-    finally:
-        N.knob("group_table_kib", None)
-
-
-@functools.lru_cache(maxsize=None)
-def _exact(rules, key):
-    """(batch, exact CPU findings) of a named input, computed once.  The findings do not
-    depend on the plan, so both list kernels share them."""
-    sc = _scanner(rules, "default")
-    name, args = key[0], key[1:]
-    if name == "mask":
-        batch = H.word_mask_batch(*args)[0]
-    elif name == "tail":
-        batch = H.tail_batch(*args)[0]
-    elif name == "entry":
-        batch = H.entry_shape_batch(*args)[0]
-    elif name == "dense":
-        batch = H.dense_batch(*args)[0]
-    elif name == "items":
-        batch = H.item_inputs(sc, args[0])[args[1]]
-    else:
-        batch = corpus.make_corpus(*args[:1], seed=args[1], plants_per_mib=300)[0]
-    return batch, sc.ScanBatch(batch, nthreads=16)
-
-
-def _run(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0, cand_capacity=0, rich=None,
-         items_cap=None):
-    """kernels() -> batch_candidates() -> check_candidates against emulate_candidates with the
-    context's settings, then scan() against the exact path.  rich: the list kernel that must
-    have run (default: k2_kernel_rich unless the scanner was compiled with small tables);
-    items_cap: the k2_items_cap knob the caller has set (groups may then be skipped).
-    Returns (stats of kernels(), reference records, reference triples)."""
-    ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, ext_cap=ext_cap, cand_capacity=cand_capacity, adapt_mib=NEVER)
-    try:
-        ctx.upload(batch)
-        ctx.kernels()
-        st = ctx.stats()
-        dev = ctx.batch_candidates()
-        n = H.nchunks_of(batch, chunk)
-        items_cap = S.default_items_cap(n) if items_cap is None else items_cap
-        ref = sc.emulate_candidates(batch, chunk, ext_cap or S.DEFAULT_EXT_CAP, word_recs=words, items_cap=items_cap)
-        _, counts = sc.emulate_items(batch, chunk, 16)
-        skipped = S.layout_reference(counts, n, items_cap)[1]["skipped"]
-        assert dev["cand_cap"] == (cand_capacity or S.DEFAULT_CAND_CAPACITY)
-        nref, ntri = H.check_candidates(dev, ref, batch, sc, chunk, skipped=skipped > 0)
-        assert st["candidates"] == nref and st["groups_skipped"] == skipped
-        assert st["overflow"] == (1 if nref > dev["cand_cap"] else 0)
-        assert st["k2_rich"] == ((0 if kernel == "small tables" else 1) if rich is None else rich), st["k2_rich"]
-        got = ctx.scan()
-        with pytest.raises(N.NativeError):  # something was submitted since kernels()
-            ctx.batch_candidates()
-    finally:
-        ctx.close()
-    assert got == want
-    return st, nref, ntri
 
 
 @pytest.fixture

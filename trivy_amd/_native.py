@@ -88,7 +88,8 @@ class Stats(C.Structure):
                 ("k1_clock_ms", C.c_double), ("chain_clock_ms", C.c_double), ("post_k1_clock_ms", C.c_double),
                 ("sum_k1_clock_ms", C.c_double), ("sum_chain_clock_ms", C.c_double),
                 ("sum_post_k1_clock_ms", C.c_double),
-                ("k2_dense_entries", C.c_uint32), ("k2_rich", C.c_uint32)]
+                ("k2_dense_entries", C.c_uint32), ("k2_rich", C.c_uint32),
+                ("k1x_img_bytes", C.c_uint32)]
 
 
 class AdaptationInfo(C.Structure):

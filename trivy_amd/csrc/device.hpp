@@ -174,6 +174,8 @@ int device_rules_adaptation(const DeviceRules* d, AdaptationView* out);
 bool device_rules_k1_filter(const DeviceRules* d);
 // true: K2's list pass runs k2_kernel_rich (decided by the occupancy API), false: k2_kernel
 bool device_rules_k2_rich(const DeviceRules* d);
+// bytes of K1X's verify image (staged in LDS up to kXImgLds), 0 without K1X
+uint32_t device_rules_k1x_img_bytes(const DeviceRules* d);
 
 int lane_create(DeviceRules* d, LaneState** out);
 void lane_destroy(LaneState* l);

@@ -60,12 +60,19 @@ void ctx_device_layer_done(tsg_ctx* c, const tsg_device_layer_stats& last);
 struct Knobs {
   std::atomic<int64_t> tar_range_kib{0}, piece_mib{0}, pike_only{0}, no_k1x{0}, emu_wordrec{0},
       x_step{0}, k1_automaton{0}, group_states{0}, group_table_kib{0}, k1f_grid{0},
-      k1f_list{0}, k2_items_cap{0}, k2_max_dense{0}, k2_no_word_recs{0}, device_poison{0};
+      k1f_list{0}, k2_items_cap{0}, k2_max_dense{0}, k2_no_word_recs{0}, device_poison{0}, grid_cap{0};
   std::mutex m;
   std::string emu_kw_unknown;
 };
 Knobs& knobs();
 std::string knob_kw_unknown();
+
+// A grid whose size comes from the device or from a constant, under the test knob grid_cap
+// (cap = its value, read once per batch or call; 0 leaves the grid as computed).  Every such
+// kernel walks its work in a loop, so fewer blocks only mean more rounds per block.
+inline int capped_grid(uint64_t grid, int64_t cap) {
+  return (int)(cap > 0 ? std::min<uint64_t>(grid, (uint64_t)cap) : grid);
+}
 
 // K2's item capacity for a batch of nchunks chunks: twice the batch's chunks (the builtin
 // rules list ~11 % of them), at least 64 Ki items; and the number of groups the dense pass

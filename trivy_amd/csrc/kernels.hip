@@ -3276,11 +3276,11 @@ static const void* k1_fn(const DevK1& k, int* threads, int* per_cu) {
 }
 
 // a persistent grid of the resident blocks (each block stages the automaton once)
-static int launch_k1(DeviceRules* r, const K1Args& A, hipStream_t st) {
+static int launch_k1(DeviceRules* r, const K1Args& A, int64_t grid_cap, hipStream_t st) {
   int threads = 0, per_cu = 0;
   const void* fn = k1_fn(r->k1, &threads, &per_cu);
   const uint64_t cap = (uint64_t)r->cus * per_cu;
-  const int grid = (int)std::min<uint64_t>((A.nitems + threads - 1) / threads, cap);
+  const int grid = capped_grid(std::min<uint64_t>((A.nitems + threads - 1) / threads, cap), grid_cap);
   DevK1 d = r->k1;
   K1Args a = A;
   void* args[] = {&d, &a};
@@ -3319,7 +3319,8 @@ static std::vector<uint32_t> hottest_over_budget(const std::vector<uint32_t>& hi
 // accepts for words like "key" that occur in most files anyway.  The device is idle
 // while the shared tables change (every lane is synchronized first).
 static int apply_unknown(DeviceRules* r, const std::shared_ptr<std::vector<uint8_t>>& kw_unknown, uint32_t ev_hot);
-static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfiles, uint64_t nchunks, uint64_t k1_items) {
+static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfiles, uint64_t nchunks, uint64_t k1_items,
+                    int64_t grid_cap) {
   const Plan& p = *r->plan;
   HIP_TRY(hipDeviceSynchronize());
   const uint32_t ns = r->k1.ns, W = r->k1.kw_words, mw = r->k1.mw;
@@ -3329,7 +3330,7 @@ static int adapt_k1(DeviceRules* r, LaneState* l, uint64_t total, uint32_t nfile
   K1Args A{l->data(), l->off, l->cf, total, nchunks, nsamp, step, r->chunk,
            nfiles, l->kw, l->ev_bits, r->d_hits, (uint32_t)kK1Seg};
   int rc;
-  if ((rc = launch_k1(r, A, l->st))) return rc;
+  if ((rc = launch_k1(r, A, grid_cap, l->st))) return rc;
   std::vector<uint32_t> hits(ns);
   HIP_TRY(hipMemcpyAsync(hits.data(), r->d_hits, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, l->st));
   HIP_TRY(hipStreamSynchronize(l->st));
@@ -3409,28 +3410,29 @@ static int upload_k1f(DeviceRules* r) {
   return TSG_OK;
 }
 
-// K1F's grid for ntiles tiles: one block per CU
-static int k1f_grid(const DeviceRules* r, uint32_t ntiles) {
+// K1F's grid for ntiles tiles: one block per CU (test knobs: at most k1f_grid blocks, and at
+// most the batch's grid_cap)
+static int k1f_grid(const DeviceRules* r, uint32_t ntiles, int64_t grid_cap) {
   const uint32_t wpb = kFThreads / 64;
   uint64_t cap = (uint64_t)r->cus;
   if (const int64_t g = knobs().k1f_grid.load()) cap = std::min<uint64_t>(cap, (uint64_t)g);  // (test knob)
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>((ntiles + wpb - 1) / wpb, cap));
+  return capped_grid(std::max<uint64_t>(1, std::min<uint64_t>((ntiles + wpb - 1) / wpb, cap)), grid_cap);
 }
 
 // K1F builds the event list itself (K1FArgs::evlist) when chunks tile its 1 KiB tiles and a
 // block's range of chunks fits the LDS bitmap
-static bool k1f_lists(const DeviceRules* r, uint32_t ntiles, uint32_t chunk) {
+static bool k1f_lists(const DeviceRules* r, uint32_t ntiles, uint32_t chunk, int64_t grid_cap) {
   if (chunk == 0 || chunk > kFTile || kFTile % chunk) return false;
   if ((r->k1f_maxlen + chunk - 1) / chunk + 1 > kFZoneChunks) return false;
-  const uint64_t grid = (uint64_t)k1f_grid(r, ntiles), wpb = kFThreads / 64, nw = grid * wpb;
+  const uint64_t grid = (uint64_t)k1f_grid(r, ntiles, grid_cap), wpb = kFThreads / 64, nw = grid * wpb;
   const uint64_t block_tiles = (wpb * ntiles + nw - 1) / nw + 1;  // (ranges differ by at most one tile per wave)
   return block_tiles * (kFTile / chunk) <= 32ull * kFBitsWords;
 }
 
 // one K1F launch over the first ntiles tiles of the batch
-static int launch_k1f(DeviceRules* r, const K1FArgs& A, hipStream_t st) {
-  if (A.evlist && !k1f_lists(r, A.ntiles, A.chunk)) return fail(TSG_ERR_INTERNAL, "K1F event list without room");
-  k1f_kernel<<<k1f_grid(r, A.ntiles), kFThreads, 0, st>>>(r->k1f, A);
+static int launch_k1f(DeviceRules* r, const K1FArgs& A, int64_t grid_cap, hipStream_t st) {
+  if (A.evlist && !k1f_lists(r, A.ntiles, A.chunk, grid_cap)) return fail(TSG_ERR_INTERNAL, "K1F event list without room");
+  k1f_kernel<<<k1f_grid(r, A.ntiles, grid_cap), kFThreads, 0, st>>>(r->k1f, A);
   HIP_TRY(hipGetLastError());
   return TSG_OK;
 }
@@ -3444,7 +3446,7 @@ static int launch_k1f(DeviceRules* r, const K1FArgs& A, hipStream_t st) {
 // sample of the batch, so few words are listed for verification (profiles/r05/kv1: the
 // model-priced buckets listed 1.24 words per KiB and their verification cost 0.2 ms per GiB).
 static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint8_t* host_data, uint64_t kw_bytes,
-                     uint64_t ev_bytes) {
+                     uint64_t ev_bytes, int64_t grid_cap) {
   const Plan& p = *r->plan;
   HIP_TRY(hipDeviceSynchronize());
   const uint32_t nrec = r->k1ft.nlit;
@@ -3457,7 +3459,7 @@ static int adapt_k1f(DeviceRules* r, LaneState* l, const K1FArgs& A0, const uint
   A.evlist = nullptr;
   A.nev = nullptr;
   int rc;
-  if ((rc = launch_k1f(r, A, l->st))) return rc;
+  if ((rc = launch_k1f(r, A, grid_cap, l->st))) return rc;
   std::vector<uint32_t> hits(std::max<uint32_t>(1, nrec));
   HIP_TRY(hipMemcpyAsync(hits.data(), r->d_fhits, sizeof(uint32_t) * hits.size(), hipMemcpyDeviceToHost, l->st));
   // the sampling launch ORed the old tables' bits and events into the batch's own arrays:
@@ -3661,6 +3663,7 @@ int device_rules_adaptation(const DeviceRules* d, AdaptationView* out) {
 }
 bool device_rules_k1_filter(const DeviceRules* d) { return d->use_k1f; }
 bool device_rules_k2_rich(const DeviceRules* d) { return d->k2_rich; }
+uint32_t device_rules_k1x_img_bytes(const DeviceRules* d) { return d->has_k1x ? d->k1x.img_bytes : 0u; }
 
 int lane_create(DeviceRules* d, LaneState** out) {
   HIP_TRY(hipSetDevice(d->device));
@@ -3751,6 +3754,7 @@ struct BatchShape {
   uint64_t entries_cap, dentries_cap, zclaim_words;
   bool work;           // the gates, the item passes and K2 have something to do
   uint32_t kwg_bytes;  // the keyword -> groups table (DeviceRules::d_kwg)
+  int64_t grid_cap;    // test knob grid_cap as read for this batch: every launch sees the same value
 };
 
 static int batch_shape(const DeviceRules* r, const ScanInput& in, const HostOut* out, BatchShape* s) {
@@ -3788,6 +3792,7 @@ static int batch_shape(const DeviceRules* r, const ScanInput& in, const HostOut*
   s->dentries_cap = (uint64_t)s->max_dense * ((s->nchunks + kEntryChunks - 1) / kEntryChunks + 1);
   s->work = s->F && s->G && s->nchunks;
   s->kwg_bytes = (uint32_t)(32ull * s->W * r->GW * 8);
+  s->grid_cap = knobs().grid_cap.load();
   return TSG_OK;
 }
 
@@ -3840,7 +3845,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
         // the stage's place and under its events (no launch for a batch without bytes)
         if (in.ngather) {
           GatherArgs GA{in.dev_src, in.src_bytes, data, total, in.gather_dev, in.ngather};
-          const int ggrid = (int)std::min<uint64_t>(in.ngather, (uint64_t)std::max(r->grid, 1));
+          const int ggrid = capped_grid(std::min<uint64_t>(in.ngather, (uint64_t)std::max(r->grid, 1)), s.grid_cap);
           gather_kernel<true><<<ggrid, 256, 0, st>>>(GA);
           HIP_TRY(hipGetLastError());
         }
@@ -3850,7 +3855,8 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
         // batch; kEvH2D..kEvMeta, the H2D's place, times it)
         if (total) {
           const uint64_t words = (total + 15) / 16;
-          const int sgrid = (int)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)r->grid));
+          const int sgrid =
+              capped_grid(std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)r->grid)), s.grid_cap);
           stage_kernel<<<sgrid, 256, 0, st>>>(data, in.dev_src, total);
           HIP_TRY(hipGetLastError());
         }
@@ -3894,7 +3900,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     if (too_many) return fail(TSG_ERR_INTERNAL, "more zero fills than the prep kernel takes");
     const uint64_t work = std::max<uint64_t>(
         {PA.ncf, (uint64_t)s.F * s.W / 4, s.one_copy ? 1 : s.tail / 16, s.k1f ? s.nchunks_pad / 4 : 1, 1});
-    const int pgrid = (int)std::min<uint64_t>((work + 255) / 256, (uint64_t)r->grid);
+    const int pgrid = capped_grid(std::min<uint64_t>((work + 255) / 256, (uint64_t)r->grid), s.grid_cap);
     prep_kernel<<<pgrid, 256, 0, st>>>(PA);
     HIP_TRY(hipGetLastError());
   }
@@ -3913,7 +3919,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   // (K1X, when a plan has it, adds events after K1: the gates pass lists them all)
   // (opt-in, knob k1f_list: kernel-only on the configs[1] batch it cost K1F ~3 us and the
   // item passes ~5 us more than the gates pass it replaces, profiles/r06/d)
-  const bool k1f_list = s.k1f && total && !r->has_k1x && knobs().k1f_list.load() && k1f_lists(r, s.k1f_tiles, s.C);
+  const bool k1f_list = s.k1f && total && !r->has_k1x && knobs().k1f_list.load() && k1f_lists(r, s.k1f_tiles, s.C, s.grid_cap);
   if (s.k1f) {
     K1FArgs A{data, l->off, l->cf, (uint32_t)total, s.C, s.F, s.k1f_tiles, s.F ? (uint32_t)s.ncf : 0u,
               l->kw, l->ev_bits, nullptr, l->counts + kCntK1F, (unsigned long long*)(l->counts + kCntClk),
@@ -3921,7 +3927,8 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     // (in.data is null unless the batch came from the pinned slot: a device-resident batch has no
     // host bytes yet, and the sample comes from the staged lane buffer)
     if (!r->adapted && total >= adapt_bytes &&
-        (rc = adapt_k1f(r, l, A, in.data, sizeof(uint32_t) * (uint64_t)s.F * s.W, sizeof(uint32_t) * s.nchunks_pad)))
+        (rc = adapt_k1f(r, l, A, in.data, sizeof(uint32_t) * (uint64_t)s.F * s.W, sizeof(uint32_t) * s.nchunks_pad,
+                        s.grid_cap)))
       return rc;
     if (k1f_list) {
       A.evlist = l->evlist;
@@ -3932,23 +3939,24 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     }
     static const bool wtrace = getenv("TSG_K1F_TRACE") != nullptr;
     if (wtrace && total) {
-      const size_t nw = (size_t)k1f_grid(r, s.k1f_tiles) * (kFThreads / 64);
+      const size_t nw = (size_t)k1f_grid(r, s.k1f_tiles, s.grid_cap) * (kFThreads / 64);
       if ((rc = l->wtrace.ensure(4 * nw))) return rc;
       HIP_TRY(hipMemsetAsync(l->wtrace, 0, sizeof(unsigned long long) * 4 * nw, st));
       A.wtrace = l->wtrace;
       l->wtrace_n = 4 * nw;
     }
-    if (total && (rc = launch_k1f(r, A, st))) return rc;
+    if (total && (rc = launch_k1f(r, A, s.grid_cap, st))) return rc;
   } else if (!r->adapted && s.k1_items >= 64 && total >= adapt_bytes) {
-    if ((rc = adapt_k1(r, l, total, s.F, s.nchunks, s.k1_items))) return rc;
+    if ((rc = adapt_k1(r, l, total, s.F, s.nchunks, s.k1_items, s.grid_cap))) return rc;
   }
   if (!s.k1f && s.k1_items) {
     K1Args A{data, l->off, l->cf, total, s.nchunks, s.k1_items, 1, s.C, s.F, l->kw, l->ev_bits, nullptr, (uint32_t)kK1Seg};
-    if ((rc = launch_k1(r, A, st))) return rc;
+    if ((rc = launch_k1(r, A, s.grid_cap, st))) return rc;
   }
   if (r->has_k1x && total) {  // the hashed literals of a large rule set, after K1's stores
-    const int xg = (int)std::max<uint64_t>(1, std::min<uint64_t>((total / 16 + kK1XBlock - 1) / kK1XBlock,
-                                                                   (uint64_t)r->cus));
+    // (one xg for both kernels: the list's slices are cap / blocks)
+    const int xg = capped_grid(
+        std::max<uint64_t>(1, std::min<uint64_t>((total / 16 + kK1XBlock - 1) / kK1XBlock, (uint64_t)r->cus)), s.grid_cap);
     K1XArgs X{data, l->off, l->cf, total, s.C, s.F, l->kw, l->ev_bits, l->xlist, l->xcount,
               (uint32_t)std::min<size_t>(l->xlist.cap, 0xFFFFFFFFu), l->counts + kCntK1X};
     void* xa[] = {(void*)&r->k1x, (void*)&X};
@@ -3991,7 +3999,9 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   if (s.work && k1f_list) {
     IA.ggate = nullptr;  // (files gated from their keyword bits in the item passes)
   } else if (s.work) {
-    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((s.nchunks + kEvPer * kBlock - 1) / (kEvPer * kBlock), (uint64_t)r->grid);
+    // (the compaction blocks take the cap; the gate blocks are one thread per file)
+    const uint32_t cgrid = (uint32_t)capped_grid(
+        std::min<uint64_t>((s.nchunks + kEvPer * kBlock - 1) / (kEvPer * kBlock), (uint64_t)r->grid), s.grid_cap);
     GateArgs GA{l->ev_bits, s.nchunks, l->evlist, l->counts + kCntEvChunks, cgrid, l->kw, s.F, s.W, r->GW, r->d_kwg, r->d_galw, l->ggate,
                 (unsigned long long*)(l->counts + kCntClk), s.kwg_bytes <= kKwgLdsMax ? s.kwg_bytes : 0u};
     gates_kernel<<<cgrid + (s.F + kBlock - 1) / kBlock, kBlock, GA.kwg_lds, st>>>(GA);
@@ -3999,7 +4009,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
   }
   if (s.work) {
     // both items passes (bcount holds grid x G); kItemsBpc blocks per CU
-    const int igrid = std::min(r->grid, r->cus * kItemsBpc);
+    const int igrid = capped_grid((uint64_t)std::min(r->grid, r->cus * kItemsBpc), s.grid_cap);
     IA.kwg_lds = !IA.ggate && s.kwg_bytes <= kItemKwgLdsMax ? s.kwg_bytes : 0u;
     const size_t ilds = item_lds_host(s.G, r->GW) + IA.kwg_lds;
     hipLaunchKernelGGL(items_count_kernel, dim3(igrid), dim3(kBlock), ilds + s.G * sizeof(uint32_t) + 16, st, IA);
@@ -4046,12 +4056,13 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     A.etrace = trace ? l->etrace.p : nullptr;
     A.clk = (unsigned long long*)(l->counts + kCntClk);
     // one block per resident slot (the grids are persistent)
+    const int k2g = capped_grid((uint64_t)r->k2_grid, s.grid_cap), k2dg = capped_grid((uint64_t)r->k2_dense_grid, s.grid_cap);
     if (r->k2_rich)
-      hipLaunchKernelGGL(k2_kernel_rich, dim3(r->k2_grid), dim3(kK2Block), r->max_lds, st, (const DevDFA*)r->d_groups, A);
+      hipLaunchKernelGGL(k2_kernel_rich, dim3(k2g), dim3(kK2Block), r->max_lds, st, (const DevDFA*)r->d_groups, A);
     else
-      hipLaunchKernelGGL(k2_kernel, dim3(r->k2_grid), dim3(kK2Block), r->max_lds, st, (const DevDFA*)r->d_groups, A);
+      hipLaunchKernelGGL(k2_kernel, dim3(k2g), dim3(kK2Block), r->max_lds, st, (const DevDFA*)r->d_groups, A);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k2_dense_kernel, dim3(r->k2_dense_grid), dim3(kBlock), r->max_lds, st,
+    hipLaunchKernelGGL(k2_dense_kernel, dim3(k2dg), dim3(kBlock), r->max_lds, st,
                        (const DevDFA*)r->d_groups, A);
     HIP_TRY(hipGetLastError());
     // (the dense pass on a second stream beside the list pass: K2 0.125 -> 0.152 ms per
@@ -4087,7 +4098,7 @@ int enqueue_scan(DeviceRules* r, LaneState* l, const ScanInput& in, HostOut* out
     OA.fb_lo = (uint32_t)p.fb_kw0;
     OA.fb_hi = (uint32_t)p.n_kw;
     OA.all_rows = r->all_kw_rows;
-    outputs_kernel<<<128, 256, 0, st>>>(OA);
+    outputs_kernel<<<capped_grid(128, s.grid_cap), 256, 0, st>>>(OA);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(out->ev[kEvDone], st));
@@ -4263,7 +4274,7 @@ int fetch_segments(DeviceFetch* f, const uint8_t* d_src, uint64_t total, uint8_t
   for (size_t k = 0; k < nsegs; k++) f->segs[k] = FetchSeg{segs[k].dst, segs[k].len};
   FetchArgs A{d_src, nullptr, f->segs_dev, (uint32_t)nsegs, total};
   HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
-  const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
+  const int grid = capped_grid(std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1)), knobs().grid_cap.load());
   return fetch_run(f, ms, [&]() -> int {
     fetch_kernel<<<grid, 256, 0, f->st>>>(A);
     HIP_TRY(hipGetLastError());
@@ -4278,7 +4289,8 @@ int gate_spans(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, const
   FetchCall call(f);
   if (call.rc) return call.rc;
   SpanGateArgs A{d_base, base_bytes, starts_dev, lengths_dev, flags_dev, nfiles};
-  const int grid = (int)std::min<uint64_t>(((uint64_t)nfiles + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
+  const int grid =
+      capped_grid(std::min<uint64_t>(((uint64_t)nfiles + 3) / 4, (uint64_t)std::max(f->d->grid, 1)), knobs().grid_cap.load());
   return fetch_run(f, ms, [&]() -> int {
     binary_gate_kernel<<<grid, 256, 0, f->st>>>(A);
     HIP_TRY(hipGetLastError());
@@ -4309,7 +4321,7 @@ int fetch_gather(DeviceFetch* f, const uint8_t* d_base, uint64_t base_bytes, uin
   std::memcpy(f->gsegs, segs, sizeof(GatherSeg) * nsegs);
   GatherArgs A{d_base, base_bytes, nullptr, dst_bytes, f->gsegs_dev, (uint32_t)nsegs};
   HIP_TRY(hipHostGetDevicePointer((void**)&A.dst, host_dst, 0));
-  const int grid = (int)std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1));
+  const int grid = capped_grid(std::min<uint64_t>(nsegs, (uint64_t)std::max(f->d->grid, 1)), knobs().grid_cap.load());
   return fetch_run(f, ms, [&]() -> int {
     gather_kernel<false><<<grid, 256, 0, f->st>>>(A);
     HIP_TRY(hipGetLastError());
@@ -4333,7 +4345,7 @@ int mark_tar(DeviceFetch* f, const uint8_t* d_tar, uint64_t tar_len, uint64_t* m
   }
   TarMarkArgs A{d_tar, tar_len, f->marks, f->marks + words, nblocks, words};
   // a wave per bitmap word, four per workgroup; past 8 workgroups per CU the grid strides
-  const int grid = (int)std::min<uint64_t>((words + 3) / 4, (uint64_t)std::max(f->d->grid, 1));
+  const int grid = capped_grid(std::min<uint64_t>((words + 3) / 4, (uint64_t)std::max(f->d->grid, 1)), knobs().grid_cap.load());
   const int rc = fetch_run(
       f, ms,
       [&]() -> int {

@@ -42,6 +42,10 @@ extern "C" int tsg_test_knob(const char* name, const char* value) {
     if (x < 0) return fail(TSG_ERR_ARG, "k1f_grid must be >= 0");
     k.k1f_grid = x;
   }
+  else if (!strcmp(name, "grid_cap")) {  // cap on every device-sized grid: many rounds per block in small tests
+    if (x < 0) return fail(TSG_ERR_ARG, "grid_cap must be >= 0");
+    k.grid_cap = x;
+  }
   else if (!strcmp(name, "device_poison")) k.device_poison = x;  // poisoned mirror of device-resident batches
   else if (!strcmp(name, "k2_no_word_recs")) k.k2_no_word_recs = x;  // transition records, not word records
   else if (!strcmp(name, "k2_items_cap")) {  // K2's item capacity (internal.hpp k2_items_cap)

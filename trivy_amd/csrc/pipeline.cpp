@@ -353,6 +353,7 @@ void update_stats(tsg_ctx* c, const Batch& b) {
   s.overflow = b.counts[kCntCand] > b.cand_cap ? 1 : 0;
   s.k2_dense_entries = b.counts[kCntDenseEntries];
   s.k2_rich = c->dr && device_rules_k2_rich(c->dr) ? 1u : 0u;
+  s.k1x_img_bytes = c->dr ? device_rules_k1x_img_bytes(c->dr) : 0u;
   s.k2_items = b.counts[kCntItems];
   s.k2_bytes = (uint64_t)b.counts[kCntItems] * c->opt.chunk_bytes;
   s.k2_launches = b.counts[kCntEntries];

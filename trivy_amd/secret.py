@@ -448,6 +448,12 @@ class Scanner:
 
 GROUP_NONE, GROUP_LIST, GROUP_DENSE, GROUP_SKIP = 0, 1, 2, 3
 ENTRY_ITEMS, ENTRY_CHUNKS = 512, 1024  # a K2 list entry's items, a dense entry's chunks
+# The kernels' block shapes (kernels.hip), for the tests that count a capped grid's rounds
+# (knob grid_cap): threads of the 256-thread kernels (kBlock; a wave per unit: four units per
+# block), chunks a compaction thread tests (kEvPer), k1x_kernel's lanes per block and 16-B
+# words per lane and round (kK1XBlock, kXWords), the largest K1X verify image staged in LDS
+# (kXImgLds), outputs_kernel's fixed grid
+BLOCK_THREADS, EV_PER, K1X_BLOCK, K1X_WORDS, K1X_IMG_LDS, OUT_BLOCKS = 256, 32, 1024, 4, 128 << 10, 128
 
 
 def default_items_cap(nchunks):
