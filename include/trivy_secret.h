@@ -620,6 +620,17 @@ int tsg_emulate_k1f(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* 
 int tsg_ruleset_rule_plan(const tsg_ruleset* rs, uint32_t rule, int32_t* group, int32_t* relax,
                           int64_t* max_len);
 
+/* Plan introspection: the rule's GPU program.  first_atom: the top-level atom the program
+ * starts at (> 0: a suffix program, the atoms before it are left to the host); rule_atoms:
+ * the top-level atoms it keeps from there (-1: all of them; >= 0: a prefix-cut program,
+ * whose candidate end is the end of that prefix, at or before the match's end); winback: how
+ * far before a candidate end the resolver lets a match start (-1: anywhere in the file);
+ * has_rev: 1 when the resolver narrows a candidate with the reverse DFA of the whole regex
+ * (never for a prefix-cut program: its candidates are no match ends).  A host-only rule
+ * and a rule without a regex report first_atom 0, rule_atoms -1 and winback -1. */
+int tsg_ruleset_rule_program(const tsg_ruleset* rs, uint32_t rule, int32_t* first_atom,
+                             int32_t* rule_atoms, int64_t* winback, int32_t* has_rev);
+
 /* Plan introspection: the rule's K1 event bits (1 run U, 2 run D, 4.. literal classes,
  * 1<<31 none), the largest distance from a GPU-program match start to its event byte,
  * and a description of the anchor. */

@@ -481,6 +481,15 @@ class _Parser:
         return ord(c)
 
 
+def parse(src):
+    """The syntax tree of a Go regexp as nested tuples: ("lit", rune, fold), ("class", ranges)
+    with folding applied, ("any",), ("anynotnl",), ("cat", items), ("alt", branches),
+    ("rep", lo, hi, greedy, sub) with hi = -1 for no upper bound, ("cap", index, sub),
+    ("group", sub), ("empty",) and the assertions ("bot",), ("eot",), ("bol",), ("eol",),
+    ("wb",), ("nwb",).  For tools that need the structure (tests/match_gen.py)."""
+    return _Parser(src).parse()
+
+
 # ---------------------------------------------------------------- emitter
 def _esc(cp):
     return "\\U%08x" % cp

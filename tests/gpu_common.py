@@ -118,11 +118,13 @@ def k2_exact(rules, key):
 
 
 def run_records(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0, cand_capacity=0, rich=None,
-                items_cap=None):
+                items_cap=None, dev_out=None):
     """kernels() -> batch_candidates() -> check_candidates against emulate_candidates with the
     context's settings, then scan() against the exact path.  rich: the list kernel that must
-    have run (default: k2_kernel_rich unless the scanner was compiled with small tables);
-    items_cap: the k2_items_cap knob the caller has set (groups may then be skipped).
+    have run (default: k2_kernel_rich unless the scanner was compiled with small tables;
+    "either": a plan whose table sizes leave the choice to the device's occupancy query);
+    items_cap: the k2_items_cap knob the caller has set (groups may then be skipped);
+    dev_out: a dict that receives what batch_candidates() read back.
     Returns (stats of kernels(), reference records, reference triples)."""
     ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, ext_cap=ext_cap, cand_capacity=cand_capacity, adapt_mib=NEVER)
     try:
@@ -139,7 +141,10 @@ def run_records(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0,
         nref, ntri = H.check_candidates(dev, ref, batch, sc, chunk, skipped=skipped > 0)
         assert st["candidates"] == nref and st["groups_skipped"] == skipped
         assert st["overflow"] == (1 if nref > dev["cand_cap"] else 0)
-        assert st["k2_rich"] == ((0 if kernel == "small tables" else 1) if rich is None else rich), st["k2_rich"]
+        if rich != "either":
+            assert st["k2_rich"] == ((0 if kernel == "small tables" else 1) if rich is None else rich), st["k2_rich"]
+        if dev_out is not None:
+            dev_out.update(dev)
         got = ctx.scan()
         with pytest.raises(N.NativeError):  # something was submitted since kernels()
             ctx.batch_candidates()

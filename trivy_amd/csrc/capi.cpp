@@ -458,6 +458,17 @@ int tsg_ruleset_rule_plan(const tsg_ruleset* rs, uint32_t rule, int32_t* group, 
   return TSG_OK;
 }
 
+int tsg_ruleset_rule_program(const tsg_ruleset* rs, uint32_t rule, int32_t* first_atom, int32_t* rule_atoms,
+                             int64_t* winback, int32_t* has_rev) {
+  if (!rs || rule >= rs->rs.rules.size()) return fail(TSG_ERR_ARG, "bad argument");
+  const Plan& p = *rs->plan;
+  if (first_atom) *first_atom = p.rule_first_atom[rule];
+  if (rule_atoms) *rule_atoms = p.rule_atoms[rule];
+  if (winback) *winback = p.rule_winback[rule];
+  if (has_rev) *has_rev = p.rule_rev[rule] ? 1 : 0;
+  return TSG_OK;
+}
+
 int tsg_ruleset_rule_anchor(const tsg_ruleset* rs, uint32_t rule, uint32_t* event, int64_t* evdist,
                             char* desc, size_t desc_len) {
   if (!rs || rule >= rs->rs.rules.size()) return fail(TSG_ERR_ARG, "bad argument");

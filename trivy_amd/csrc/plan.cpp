@@ -700,6 +700,9 @@ std::unique_ptr<Plan> build_plan(const Ruleset& rs, const PlanOptions& opt, std:
   // construction of the counted generic rules would cost more than it saves)
   for (size_t r = 0; r < R; r++) {
     if (!rs.rules[r].regex || (p->rule_winback[r] >= 0 && p->rule_winback[r] <= 1024)) continue;
+    // a prefix-cut program's candidate end is the end of the prefix, not of a match: the
+    // whole regex run backwards from it finds nothing and would drop every candidate
+    if (p->rule_atoms[r] >= 0) continue;
     DFAOptions o;
     o.max_states = 2048;
     std::string e;
@@ -1189,15 +1192,18 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
         wptr[r] = &wins[r];
       }
     // every match start lies in [end - winback, end] of some candidate end offset; the
-    // reverse DFA narrows that to [leftmost start, end] or drops the candidate
-    auto add_end = [&](RuleWindows& w, uint32_t r, int64_t end) {
+    // reverse DFA narrows that to [leftmost start, end] or drops the candidate.  K2's end of
+    // a prefix-cut program is the end of the prefix, and rule_winback the prefix's longest
+    // match; the fold-rune DFAs below run whole programs, so their ends are match ends
+    // (full_end) and get the whole rule's bound instead.
+    auto add_end = [&](RuleWindows& w, uint32_t r, int64_t end, bool full_end) {
       int64_t lo;
       if (const DFA* rev = plan.rule_rev[r].get()) {
         lo = reverse_match_start(*rev, content, end);
         if (lo < 0) return;
         lo = align_rune(content, n, lo);
       } else {
-        const int64_t back = plan.rule_winback[r];
+        const int64_t back = full_end && plan.rule_atoms[r] >= 0 ? plan.rule_maxlen[r] : plan.rule_winback[r];
         lo = back < 0 ? 0 : align_rune(content, n, std::max<int64_t>(0, end - back));
       }
       w.iv.push_back({lo, end});
@@ -1226,7 +1232,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
             w.whole = true;
             w.iv.clear();
           } else {
-            add_end(w, r, cand[j].end);
+            add_end(w, r, cand[j].end, false);
           }
         }
         normalize(w);
@@ -1286,7 +1292,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
                         const auto& m = fd.masks[mi];
                         for (size_t k = 0; k < nf; k++)
                           if (want[k] && ((m[k / 64] >> (k % 64)) & 1))
-                            add_end(wins[plan.fold_rules[k]], plan.fold_rules[k], (int64_t)pos);
+                            add_end(wins[plan.fold_rules[k]], plan.fold_rules[k], (int64_t)pos, true);
                       });
           if (prof) tdfa += __rdtsc() - td;
           for (size_t k = 0; k < nf; k++)
@@ -1316,7 +1322,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
           w.iv.clear();
           const uint64_t td = prof ? __rdtsc() : 0;
           run_segment(*fd, content, 0, (uint64_t)n, 0, (uint64_t)n, ~0u, [&](uint32_t mi, uint64_t pos) {
-            if (fd->masks[mi][0] & 1) add_end(w, (uint32_t)r, (int64_t)pos);
+            if (fd->masks[mi][0] & 1) add_end(w, (uint32_t)r, (int64_t)pos, true);
           });
           if (prof) tdfa += __rdtsc() - td;
         } else if (plan.rule_group[r] >= 0 && plan.rule_relax[r] < 0) {
@@ -1329,7 +1335,7 @@ void resolve_batch(const Ruleset& rs, const Plan& plan, const BatchView& b,
           w.iv.clear();
           const uint64_t td = prof ? __rdtsc() : 0;
           run_segment(d, content, 0, (uint64_t)n, 0, (uint64_t)n, ~0u, [&](uint32_t mi, uint64_t pos) {
-            if ((d.masks[mi][local / 64] >> (local % 64)) & 1) add_end(w, (uint32_t)r, (int64_t)pos);
+            if ((d.masks[mi][local / 64] >> (local % 64)) & 1) add_end(w, (uint32_t)r, (int64_t)pos, true);
           });
           if (prof) tdfa += __rdtsc() - td;
         } else {

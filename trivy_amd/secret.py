@@ -373,6 +373,23 @@ class Scanner:
         N.check(N.lib().tsg_ruleset_rule_plan(self.handle, rule, C.byref(g), C.byref(relax), C.byref(ml)))
         return g.value
 
+    def rule_plan(self, rule):
+        """Plan introspection (tsg_ruleset_rule_plan): the rule's K2 group (-1: host only),
+        relaxation (-1: exact) and longest match in bytes (-1: unbounded)."""
+        g, relax, ml = C.c_int32(), C.c_int32(), C.c_int64()
+        N.check(N.lib().tsg_ruleset_rule_plan(self.handle, rule, C.byref(g), C.byref(relax), C.byref(ml)))
+        return {"group": g.value, "relax": relax.value, "maxlen": ml.value}
+
+    def rule_program(self, rule):
+        """Plan introspection (tsg_ruleset_rule_program): the rule's GPU program: first_atom
+        (> 0: a suffix program), rule_atoms (>= 0: a prefix-cut program), the resolver's
+        rule_winback and whether it has a reverse DFA (rule_rev)."""
+        fa, at, wb, rev = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        N.check(N.lib().tsg_ruleset_rule_program(self.handle, rule, C.byref(fa), C.byref(at), C.byref(wb),
+                                                 C.byref(rev)))
+        return {"first_atom": fa.value, "rule_atoms": at.value, "rule_winback": wb.value,
+                "rule_rev": bool(rev.value)}
+
     def k1_literals(self):
         """K1's literals as (bytes, event bits); ids below n_keywords are keywords."""
         out = []
