@@ -643,6 +643,12 @@ int tsg_ruleset_rule_anchor(const tsg_ruleset* rs, uint32_t rule, uint32_t* even
 int tsg_ruleset_k1_literal(const tsg_ruleset* rs, uint32_t i, uint8_t* buf, uint32_t cap,
                            uint32_t* len, uint32_t* event);
 
+/* Test hook: a 64-bit FNV-1a hash of a canonical serialisation of every member of the
+ * compiled plan (K1 and K1X literals, every DFA's tables, every rule's program, anchor and
+ * windows, the groups): two rule sets compiled to the same plan give the same digest, on any
+ * number of CPUs. */
+int tsg_ruleset_plan_digest(const tsg_ruleset* rs, uint64_t* out);
+
 /* Emulate K1+K2 on the CPU with the GPU algorithm and resolve (tests). */
 int tsg_scan_batch_emulated(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets,
                             uint32_t nfiles, const char* paths, const uint64_t* path_offsets,

@@ -72,9 +72,26 @@ def test_k1x_split_per_step(knob):
         N.knob("x_step", "3")
 
 
-@pytest.mark.parametrize("chunk", [64, 256])
-def test_user_rules_emulation_vs_exact(user100, chunk):
-    doc, sc = user100
+@pytest.fixture(scope="module")
+def user100_no_k1x():
+    """The user100 set under the no_k1x knob: no K1X literals, the K1 automaton fits its table
+    by leaving keywords out, longest first (their rules' gates are checked on the host)."""
+    from trivy_amd import _native as N
+    doc = configs.user_rules_doc(100, seed=4)
+    N.knob("no_k1x", 1)
+    try:
+        sc = S.NewScanner(S.config_from_dict(doc))
+    finally:
+        N.knob("no_k1x", None)
+    assert sc.info()["k1x_literals"] == 0
+    return doc, sc
+
+
+@pytest.mark.parametrize("rules,chunk", [("user100", 64), ("user100", 256), ("user100_no_k1x", 64),
+                                         ("user100_no_k1x", 256)],
+                         ids=["64", "256", "no_k1x-64", "no_k1x-256"])
+def test_user_rules_emulation_vs_exact(request, rules, chunk):
+    doc, sc = request.getfixturevalue(rules)
     b = S.Batch.from_args(configs.mixed_batch(doc, 192 << 10, seed=40 + chunk))
     want = sc.ScanBatch(b, nthreads=8)
     assert sc.ScanBatch(b, emulate_chunk=chunk) == want

@@ -4,7 +4,7 @@ CPU path and the oracle, on seeded synthetic corpora.  No GPU needed.
 
 The fold-rune corpus stresses the one place where the kernels' anchors are not exact:
 U+212A (K) and U+017F (s) join ASCII letters under (?i) and U+0130 lowercases to 'i'
-(bytes.ToLower), so the resolver must add windows around them (plan.cpp resolve_batch).
+(bytes.ToLower), so the resolver must add windows around them (resolve.cpp resolve_batch).
 Whether Go treats these runes this way is not pinned by any reference fixture: the
 expected behaviour follows Go 1.19's unicode.SimpleFold / unicode.ToLower tables
 (Appendix A.6/A.7 of SURVEY.md) as restated by oracle/gounicode.py.
@@ -121,7 +121,7 @@ def test_fold_runes_unbounded_rules_emulated_vs_exact(builtin, chunk):
 def test_word_records_emulated_vs_exact(builtin, chunk, knob):
     """K2's word records (kernels.hip Lane::accept_word: one record per accepting 16-B word,
     in the chunk and in the tail) as the emulation writes them ("emu_wordrec" knob): the host's
-    replay and expansion of each word (plan.cpp resolve_batch) gives the exact results, on
+    replay and expansion of each word (resolve.cpp resolve_batch) gives the exact results, on
     the seeded corpus, on fold-rune files and on accept-dense long tokens."""
     knob("emu_wordrec", 1)
     batch, _ = corpus.make_corpus(3 << 20, seed=70 + chunk, plants_per_mib=60)
@@ -144,7 +144,7 @@ def test_fold_rune_then_immortal_tail_emulated_vs_exact(chunk):
     folding rune the resolver's combined fold-DFA pass follows its threads in noinject mode,
     and a thread inside `(?s).*` never dies (DFA::immortal).  That pass stops there; the
     rule must then be resolved over the whole file, or every match end past that point (the
-    `omega` far after the rune) is lost (plan.cpp resolve_batch)."""
+    `omega` far after the rune) is lost (resolve.cpp resolve_batch)."""
     doc = {"rules": [{"id": "kilo-omega", "category": "user", "title": "kilo to omega", "severity": "HIGH",
                       "regex": r"(?i)kilo(?P<secret>(?s).*)omega", "secret-group-name": "secret",
                       "keywords": ["omega"]}]}

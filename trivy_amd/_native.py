@@ -271,6 +271,7 @@ SIGNATURES = [
                                   C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint64)]),
     ("tsg_ruleset_k1_literal", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("tsg_ruleset_plan_digest", C.c_int, [_P, _U64P]),
 ]
 
 _lib = None

@@ -491,6 +491,12 @@ int tsg_ruleset_k1_literal(const tsg_ruleset* rs, uint32_t i, uint8_t* buf, uint
   return TSG_OK;
 }
 
+int tsg_ruleset_plan_digest(const tsg_ruleset* rs, uint64_t* out) {
+  if (!rs || !out) return fail(TSG_ERR_ARG, "bad argument");
+  *out = plan_digest(*rs->plan);
+  return TSG_OK;
+}
+
 int tsg_go_sort_perm(const uint8_t* keys, const uint64_t* key_offsets, const int64_t* secondary,
                      uint32_t n, uint32_t* perm) {
   if ((n && (!keys || !key_offsets || !perm))) return fail(TSG_ERR_ARG, "bad argument");

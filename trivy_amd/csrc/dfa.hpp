@@ -104,4 +104,47 @@ inline const std::string& never_literal() {
   return s;
 }
 
+// One lane's work on one file segment [a, b) of file [fs, fe): inject mode over the
+// segment, then (if the file continues) noinject mode until every thread started in
+// the segment has died.  on_acc(mask_index, position_in_file).
+template <class OnAcc>
+bool run_segment(const DFA& d, const uint8_t* data, uint64_t fs, uint64_t fe, uint64_t a,
+                 uint64_t b, uint32_t ext_cap, OnAcc on_acc) {
+  const int nc = d.nclasses;
+  uint32_t s = (a == fs) ? d.start[kCtxBOT] : d.start[DFA::ctx_of(data[a - 1], d)];
+  if (!d.packed.empty()) {  // one load per byte: next row | accept | next dead (DFA::pack)
+    uint32_t row = s * (uint32_t)nc;
+    for (uint64_t p = a; p < b; p++) {
+      const uint32_t e = row + d.cls[data[p]];
+      const uint32_t x = d.packed[e];
+      if (x >> 31) on_acc(d.acc[e], p - fs);
+      row = x & 0x3FFFFFFFu;
+    }
+    s = row / (uint32_t)nc;
+  }
+  for (uint64_t p = d.packed.empty() ? a : b; p < b; p++) {
+    size_t e = (size_t)s * nc + d.cls[data[p]];
+    if (d.acc[e]) on_acc(d.acc[e], p - fs);
+    s = d.next[e];
+  }
+  if (b >= fe) {
+    if (d.eot_acc[s]) on_acc(d.eot_acc[s], fe - fs);
+    return false;
+  }
+  s = d.to_noinject[s];
+  uint64_t p = b;
+  while (p < fe && !d.dead[s]) {
+    // at the kernels' 16-byte word boundaries: past ext_cap, or in a state whose threads
+    // never die (the tail would run to the end of the file) -> the host resolves the
+    // file whole
+    if ((p == b || (p & 15) == 0) && (p - b >= ext_cap || d.immortal[s])) return true;
+    size_t e = (size_t)s * nc + d.cls[data[p]];
+    if (d.acc[e]) on_acc(d.acc[e], p - fs);
+    s = d.next[e];
+    p++;
+  }
+  if (p == fe && !d.dead[s] && d.eot_acc[s]) on_acc(d.eot_acc[s], fe - fs);
+  return false;
+}
+
 }  // namespace tsg

@@ -32,7 +32,7 @@ constexpr int32_t kHighByteRune = 0x110000;
 using Ranges = std::vector<std::pair<int32_t, int32_t>>;  // sorted, non-overlapping
 
 // Shape of one element of a regex's flattened top-level concatenation, for choosing
-// the GPU anchor of a rule (plan.cpp).  Runes U+017F / U+212A (the only non-ASCII
+// the GPU anchor of a rule (plan.cpp choose_anchor).  Runes U+017F / U+212A (the only non-ASCII
 // members (?i) adds to ASCII letters) are ignored: files containing them are resolved
 // whole on the host.
 struct AtomInfo {

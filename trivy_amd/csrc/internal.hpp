@@ -1,4 +1,4 @@
-// Shared internals of the C ABI (capi.cpp, gpu.hip).
+// Shared internals of the C ABI (capi.cpp, pipeline.cpp, layer.cpp, multi.cpp, kernels.hip).
 #pragma once
 #include <algorithm>
 #include <atomic>

@@ -821,7 +821,7 @@ void gate_and_pack(const uint8_t* tar, const Gate& g, const std::vector<Walked>&
   const bool prof = getenv("TSG_LAYER_PROF") != nullptr;
   auto t1 = now();
   const size_t n = walked.size();
-  const int T = 16;  // the process-wide host pool (plan.cpp)
+  const int T = 16;  // the process-wide host pool (pool.cpp)
   const std::vector<size_t> kept = gate_kept(tar, g, walked, L);
   auto t2 = now();
   std::vector<uint64_t> dst(n);
@@ -1517,7 +1517,7 @@ int fs_collect(const tsg_ruleset* rs, const char* root, const char* const* skip_
       const size_t k = r0.rfind('/');
       directory = k == std::string::npos ? "." : (k == 0 ? "/" : r0.substr(0, k));
     }
-    const int T = 16;  // the process-wide host pool (plan.cpp)
+    const int T = 16;  // the process-wide host pool (pool.cpp)
     const auto t_walk0 = std::chrono::steady_clock::now();
     std::vector<std::unique_ptr<FsFile>> files;
     uint32_t walked = 0;

@@ -9,7 +9,7 @@
 // that device's pinned slots, submitted on the context's own lanes, and the serialized
 // per-file results are gathered back in input order on the host.  There is no collective:
 // files are independent (scanner.go:341).  The resolver pool is process-wide
-// (plan.cpp Pool), so N contexts share its threads instead of multiplying them.
+// (pool.cpp), so N contexts share its threads instead of multiplying them.
 #include <algorithm>
 #include <cstring>
 #include <memory>

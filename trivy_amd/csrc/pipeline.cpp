@@ -4,7 +4,7 @@
 // A batch = the files of one pinned slot.  Submitting it puts its whole device part on one
 // lane's stream (device.hpp enqueue_scan: H2D, K1, gates, device-side layout, K2, outputs
 // back to pinned host buffers) and starts its host job, which waits for the lane's
-// completion event and resolves the candidates exactly (plan.cpp resolve_batch).  With
+// completion event and resolves the candidates exactly (resolve.cpp resolve_batch).  With
 // two lanes, the H2D of batch i+1 overlaps the kernels of batch i, and the host
 // resolution of earlier batches runs on the resolver pool meanwhile.  Nothing here waits
 // for the device except the jobs (and tsg_batch_kernels, a synchronous test hook).
@@ -548,7 +548,7 @@ void run_job(tsg_ctx* c, std::shared_ptr<Batch> b, BatchView view, HostOut ho,
       kv.overflow = ho.ovf;
       kv.sparse_kw = true;  // outputs_kernel: flags and the keyword rows the host reads
       kv.kw_unknown = kwu ? kwu->data() : nullptr;
-      kv.path_ok = nullptr;  // Global.AllowPath on the host (plan.cpp path_allowed)
+      kv.path_ok = nullptr;  // Global.AllowPath on the host (resolve.cpp path_allowed)
       kv.group_skipped = skipped ? ho.gskip : nullptr;
     }
     // a batch from the caller's HBM: the slot holds no content yet; fetch what the resolver reads

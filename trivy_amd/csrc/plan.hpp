@@ -108,10 +108,13 @@ struct PlanOptions {
   int max_group_table_bytes = 48 * 1024;
   int max_rules_per_group = 64;
   int max_kw_table_bytes = 96 * 1024;  // K1 transition table must stay LDS-resident
-  bool anchors = true;                 // event windows (false: scan whole gated files)
 };
 
 std::unique_ptr<Plan> build_plan(const Ruleset& rs, const PlanOptions& opt, std::string* err);
+
+// 64-bit FNV-1a hash of a canonical serialisation of every member of the plan (test hook
+// tsg_ruleset_plan_digest): equal digests, equal plans.
+uint64_t plan_digest(const Plan& p);
 
 // One GPU candidate: rule `rule` has a match ending at byte `end` of file `file`, or, with
 // end == kCandWhole, the rule's K2 thread ran past ext_cap: resolve the rule over the whole

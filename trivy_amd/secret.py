@@ -287,6 +287,13 @@ class Scanner:
         N.check(N.lib().tsg_ruleset_get_info(self._h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in N.RulesetInfo._fields_}
 
+    def plan_digest(self):
+        """Test hook (tsg_ruleset_plan_digest): a 64-bit hash of every member of the compiled
+        plan; two plans with the same digest are the same plan."""
+        d = C.c_uint64()
+        N.check(N.lib().tsg_ruleset_plan_digest(self._h, C.byref(d)))
+        return d.value
+
     def k1_reference(self, batch, chunk):
         """K1 semantics on the CPU (same layout as GpuContext.k1_output)."""
         import numpy as np
