@@ -631,6 +631,17 @@ int tsg_ruleset_rule_plan(const tsg_ruleset* rs, uint32_t rule, int32_t* group, 
 int tsg_ruleset_rule_program(const tsg_ruleset* rs, uint32_t rule, int32_t* first_atom,
                              int32_t* rule_atoms, int64_t* winback, int32_t* has_rev);
 
+/* Test hook: K2 group `group` of the plan.  nrules: its rule count (at most 64); rules: the
+ * first min(nrules, cap) global rule indices in the group's local order (a rule's position is
+ * its bit in the group DFA's accept masks); per_state: the accept layout of the group's
+ * device table, from the decision the upload makes (dfa_layout.hpp) -- 1: every transition
+ * out of a state has the same accepts, which are staged per state in LDS; 0: look-ahead, the
+ * accepts differ per byte class (a trailing empty-width assertion) and are read per
+ * transition.  Needs no device.  Any output pointer may be NULL; a group index past the plan
+ * is TSG_ERR_ARG. */
+int tsg_ruleset_group_table(const tsg_ruleset* rs, uint32_t group, uint32_t* nrules,
+                            int32_t* per_state, uint32_t* rules, uint32_t cap);
+
 /* Plan introspection: the rule's K1 event bits (1 run U, 2 run D, 4.. literal classes,
  * 1<<31 none), the largest distance from a GPU-program match start to its event byte,
  * and a description of the anchor. */

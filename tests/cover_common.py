@@ -44,6 +44,64 @@ FOLDCUT_RULES = [
      "regex": r"(?i)qqtoken=kabcdefghij[a-j]+END", "keywords": ["qqtoken"]},
 ]
 
+# Empty-width assertions: every operation (^ $ \A \z (?m)^ (?m)$ \b \B) leading and trailing,
+# \b and a line anchor inside an alternation or between atoms, beside a rule without any.
+# (id, regex, keyword or None, the core string that tests/match_gen.py's context matrix puts
+# between every `before` and `after` context.)  Each keyword is its rule's literal.
+ASSERT_RULES = (
+    ("mla", r"(?m)^mla=[a-f0-9]{8}$", "mla=", b"mla=0123abcd"),
+    ("mlb", r"(?m)^mlb=[a-f0-9]{8}", "mlb=", b"mlb=0123abcd"),
+    ("mlc", r"mlc=[a-f0-9]{8}(?m:$)", "mlc=", b"mlc=0123abcd"),
+    ("wbd", r"\bwbd[0-9]{4}\b", "wbd", b"wbd1234"),
+    ("wbe", r"wbe[0-9]{4}\b", "wbe", b"wbe1234"),
+    ("nwf", r"\Bnwf[0-9]{4}\B", "nwf", b"nwf1234"),
+    ("atg", r"\Aatg=[a-z]{4,9}", "atg=", b"atg=abcde"),
+    ("zth", r"zth=[a-z]{4,9}\z", "zth=", b"zth=abcde"),
+    ("csi", r"(?:^|,)csi=[a-z]{6}(?:,|$)", "csi=", b"csi=abcdef"),
+    ("mlj", r"(?m)(?:^|\s)mlj\s*=\s*(?P<secret>[A-Za-z0-9]{12})\r?$", "mlj", b"mlj = Ab3dEf6hIj9l"),
+    ("kwk", r"(?i)\bkwk_[a-z0-9]{10}\b", "kwk_", b"KwK_a1B2c3D4e5"),
+    ("bgl", r"(?s)(?m)^bgl\{.*?\}$", "bgl{", b"bgl{ab\ncd}"),
+    ("lzm", r"(?U)lzm=[a-z]+;", "lzm=", b"lzm=abc;"),
+    ("wbn", r"wbn\b.\b[a-z]{3}", "wbn", b"wbn-abc"),
+    ("up24", r"\b[A-Z0-9]{24}\b", None, b"AB12CD34EF56GH78IJ90KL12"),
+    ("hex32", r"(?m)^[a-f0-9]{32}$", None, b"0123456789abcdef0123456789abcdef"),
+    ("rud", r"(?m)^\s*rud\s*[:=]\s*[A-Za-z0-9+/]{20,}={0,2}$", "rud", b"rud: QWxhZGRpbjpvcGVuIHNlc2FtZQ=="),
+    ("rue", r"(?i)(?:^|[^a-z0-9])rue[a-z0-9]{16}(?:[^a-z0-9]|$)", "rue", b"rueabcdefgh12345678"),
+    ("ruf", r"(?m)^ruf-[a-z]+-[0-9]+\r?$", "ruf-", b"ruf-abc-123"),
+    ("rug", r"(?s)\Arug.*zz\z", "rug", b"rug middle zz"),
+)
+ASSERT_CORE = {r[0]: r[3] for r in ASSERT_RULES}
+
+# One DFA of max_rules_per_group = 64 rules: 70 rules gq<xy>_[0-9]{4} whose tails rotate through
+# \b, nothing and $ in pairs (rule i: tail i // 2 % 3), so that the rules with local index 0, 31,
+# 32 and 63 of the full group can all match in the middle of a file, and a rule without a
+# length bound.
+GROUP64_TAILS = (r"\b", "", "$")
+GROUP64_N = 70
+GROUP64_UNB = "gqzz"
+
+
+def _gq(i):
+    return "gq" + "abcdefghij"[i // 10] + "klmnopqrst"[i % 10]
+
+
+def _rule(rid, regex, keyword):
+    d = {"id": rid, "category": "t", "title": rid, "severity": "LOW", "regex": regex}
+    if keyword:
+        d["keywords"] = [keyword]
+    return d
+
+
+def assert_doc():
+    return {"enable-builtin-rules": [H.AKIA_GROUP_RULE], "rules": [_rule(i, rx, kw) for i, rx, kw, _ in ASSERT_RULES]}
+
+
+def group64_doc():
+    rules = [_rule(_gq(i), _gq(i) + "_[0-9]{4}" + GROUP64_TAILS[i // 2 % 3], _gq(i) + "_") for i in range(GROUP64_N)]
+    rules.append(_rule(GROUP64_UNB, r"(?s)gqzz\{.*\}", "gqzz{"))
+    return {"enable-builtin-rules": [H.AKIA_GROUP_RULE], "rules": rules}
+
+
 
 def _scanner(doc, group_states=None):
     if group_states is not None:
@@ -64,8 +122,9 @@ def _user40_doc():
 @functools.lru_cache(maxsize=None)
 def rule_set(name):
     """(scanner, the indices of the rules that the set's batch has files for).  Names:
-    ("builtin", group_states), "blob", "foldcut", "k2", "hostonly", "user40"."""
-    if isinstance(name, tuple):
+    ("builtin", group_states), "blob", "foldcut", "k2", "hostonly", "user40", "assert",
+    ("assert", 24), "group64"."""
+    if isinstance(name, tuple) and name[0] == "builtin":
         sc = _scanner(None, name[1])
         return sc, tuple(range(len(sc.Rules)))
     if name == "blob":
@@ -78,6 +137,12 @@ def rule_set(name):
         sc = H.hostonly_scanner()
     elif name == "user40":
         sc = _scanner(_user40_doc())
+    elif name == "assert":
+        sc = _scanner(assert_doc())
+    elif name == ("assert", 24):
+        sc = _scanner(assert_doc(), 24)
+    elif name == "group64":
+        sc = _scanner(group64_doc())
     else:
         raise ValueError(name)
     builtin = {r.ID for r in S.builtin_rules()[0]}
@@ -88,7 +153,11 @@ def set_id(name):
     return name if isinstance(name, str) else "%s-%s" % (name[0], "default" if name[1] is None else name[1])
 
 
-ALL_SETS = tuple(("builtin", g) for g in GROUP_STATES) + ("blob", "foldcut", "k2", "hostonly", "user40")
+ALL_SETS = tuple(("builtin", g) for g in GROUP_STATES) + ("blob", "foldcut", "k2", "hostonly", "user40",
+                                                           "assert", ("assert", 24), "group64")
+# the sets whose batches keep the files in which the oracle finds nothing: what catches a
+# spurious finding
+KEEP_UNMATCHED = ("assert", "group64")
 
 
 @dataclass
@@ -109,7 +178,8 @@ def _batch_of(meta, rule, truth):
 # run): tests/golden/candidate_cover/<set>.json.gz, written by
 # `python -m tests.cover_common`; tests/test_candidate_cover.py checks that they are what the
 # generator and the oracle give today.
-FIXTURE_SETS = {"builtin": ("builtin", None), "user40": "user40", "foldcut": "foldcut"}
+FIXTURE_SETS = {"builtin": ("builtin", None), "user40": "user40", "foldcut": "foldcut", "assert": "assert",
+                "group64": "group64"}
 
 
 def _fixture_path(key):
@@ -142,15 +212,60 @@ def write_fixtures():
         print("%s: %d files, %d bytes" % (_fixture_path(key), len(cb.meta), os.path.getsize(_fixture_path(key))))
 
 
+def _context_files(ru, take):
+    """The "assert" set's files of one rule: the full (before, after) product wherever it
+    falls, then every single context on the scan's geometry and the file-boundary pairs
+    (tests/match_gen.py), the partner context of a single one being the first with which the
+    oracle found a match in the product."""
+    core = ASSERT_CORE[ru.ID]
+    hit = [gf.variant.split("|") for gf in G.context_product(ru.ID, core) if take(gf)]
+    before = next((b for b in G.BEFORE if any(h[0] == b[0] for h in hit)), G.BEFORE[1])
+    after = next((a for a in G.AFTER if any(h[1] == a[0] for h in hit)), G.AFTER[1])
+    for gf in G.context_geometry(ru.ID, core, before, after):
+        take(gf)
+
+
+def _group64_files(sc, r, own):
+    """The "group64" set's files of rule r: the rule's shortest match at the end of a file
+    and in the middle of one before a word character; for two rules the file with every
+    rule's match on a line of its own; for the unbounded rule a body of 40,000 bytes (most of
+    the batch: at chunk 128 the full group has fewer items than half the chunks and is
+    listed); and, with the first rule of a group's upper half (local index 32), a file in
+    which one 16-byte word of the batch holds the ends of two matches of rules with local
+    index >= 32."""
+    ru = sc.Rules[r]
+    k = own.index(r)
+    if ru.ID == GROUP64_UNB:
+        return [G.GenFile(ru.ID, "g64", "unbounded", "long", b"qz gqzz{" + G.filler(40000) + b"} qz\n", False)]
+    m = ("%s_%04d" % (ru.ID, k)).encode()
+    out = [G.GenFile(ru.ID, "g64", "eof", "word/eof", b"qz " + m, False),
+           G.GenFile(ru.ID, "g64", "mid", "mid/word", b"qz " + m + b"x qz\n", False)]
+    if k % 35 == 0:
+        lines = b"".join(("%s_%04d\n" % (sc.Rules[q].ID, j)).encode() for j, q in enumerate(own)
+                         if sc.Rules[q].ID != GROUP64_UNB)
+        out.append(G.GenFile(ru.ID, "g64", "all", "lines", lines, False))
+    local = sc.group_table(sc.rule_group(r))["rules"]
+    if len(local) > 32 and local[32] == r:
+        # two rules of the upper half whose match may end before a space; the first match
+        # ends at byte 17 of a file that starts a chunk, the second at byte 27
+        two = [q for q in local[32:] if not sc.Rules[q].Regex.endswith("$")]
+        a, b = (("%s_%04d" % (sc.Rules[q].ID, 7)).encode() for q in (two[0], two[-1]))
+        for q in (two[0], two[-1]):
+            out.append(G.GenFile(sc.Rules[q].ID, "g64", "two-ends", "word16@0", b"qz vx qz" + a + b" " + b + b" qz\n", False))
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def cover_batch(name, reduced=True):
     """The generated files of a rule set in which the oracle finds a match of the file's
-    rule (neighbour files are kept as they are).  It depends on the rules only: the builtin
-    sets share one batch."""
+    rule (neighbour files are kept as they are; in the KEEP_UNMATCHED sets every file is
+    kept).  It depends on the rules only: the builtin sets share one batch, and so do the
+    plans of "assert"."""
     from oracle import goregex
     if isinstance(name, tuple) and name[1] is not None:
-        return cover_batch(("builtin", None), reduced)
+        return cover_batch((name[0], None) if name[0] == "builtin" else name[0], reduced)
     sc, own = rule_set(name)
+    keep_all = name in KEEP_UNMATCHED
     meta, rule, truth = [], [], []
     for r in own:
         ru = sc.Rules[r]
@@ -160,10 +275,10 @@ def cover_batch(name, reduced=True):
         kws = [k.lower().encode() for k in ru.Keywords]
         kept = set()
 
-        def take(gf):
+        def take(gf, r=r):
             gated = not kws or any(k in gf.body.lower() for k in kws)
             found = [tuple(m) for m in rx.FindAllIndex(gf.body)] if gated else []
-            if not found and not gf.aux:
+            if not found and not gf.aux and not keep_all:
                 return False
             meta.append(gf)
             rule.append(r)
@@ -172,6 +287,20 @@ def cover_batch(name, reduced=True):
                 kept.add(gf.cls)
             return bool(found)
 
+        if name == "assert":
+            _context_files(ru, take)
+            continue
+        if name == "group64":
+            ids = {x.ID: i for i, x in enumerate(sc.Rules)}
+            for gf in _group64_files(sc, r, list(own)):
+                if gf.rule == ru.ID:
+                    take(gf)
+                else:   # (the second rule of the two-ends file)
+                    rx2 = goregex.MustCompile(sc.Rules[ids[gf.rule]].Regex)
+                    meta.append(gf)
+                    rule.append(ids[gf.rule])
+                    truth.append([tuple(m) for m in rx2.FindAllIndex(gf.body)])
+            continue
         for gf in G.files_for(ru.ID, ru.Regex, list(ru.Keywords), seed=r, reduced=reduced):
             take(gf)
         # a class whose variants matched at none of their rotating placements (a rule that
@@ -181,14 +310,15 @@ def cover_batch(name, reduced=True):
                 any(take(gf) for gf in G.files_for(ru.ID, ru.Regex, list(ru.Keywords), seed=r, reduced=False,
                                                    only=(cls,)) if not gf.aux)
     # The chunks and words are the batch's, not the file's: a file whose placement aims at a
-    # chunk or word boundary starts on a multiple of 256 bytes of the batch, behind a filler
-    # file of the bytes that takes.
+    # chunk or word boundary starts on a multiple of 256 bytes of the batch (a context file:
+    # at its own offset modulo 256, G.phase_of), behind a filler file of the bytes that takes.
     meta0, rule0, truth0 = meta, rule, truth
     meta, rule, truth = [], [], []
     at = 0
     for m, r, t in zip(meta0, rule0, truth0):
-        if m.placement in G.ALIGNED and at % 256:
-            pad = G.GenFile(m.rule, m.cls, m.variant, "filler", G.filler(256 - at % 256), False, True)
+        ph = G.phase_of(m)
+        if ph is not None and at % 256 != ph:
+            pad = G.GenFile(m.rule, m.cls, m.variant, "filler", G.filler((ph - at) % 256), False, True)
             meta.append(pad)
             rule.append(r)
             truth.append([])

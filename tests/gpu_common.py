@@ -87,6 +87,9 @@ def k2_scanner_for(rules, kernel):
             return H.k2_scanner()
         if rules == "user":
             return S.NewScanner(S.config_from_dict(configs.user_rules_doc(1000, 4)))
+        if rules in ("assert", "group64"):   # the rule sets of tests/cover_common.py
+            from tests import cover_common as CC
+            return S.NewScanner(S.config_from_dict(CC.assert_doc() if rules == "assert" else CC.group64_doc()))
         return S.NewScanner(None)
     finally:
         N.knob("group_table_kib", None)
@@ -105,6 +108,11 @@ def k2_input(sc, key):
         return H.dense_batch(*args)[0]
     if name == "items":
         return H.item_inputs(sc, args[0])[args[1]]
+    if name == "cover":   # a committed batch of tests/golden/candidate_cover/
+        from tests import cover_common as CC
+        return CC.fixture_batch(args[0]).batch
+    if name == "hex lines":
+        return H.hex_lines_batch(*args)
     return corpus.make_corpus(*args[:1], seed=args[1], plants_per_mib=300)[0]
 
 

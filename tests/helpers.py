@@ -277,6 +277,17 @@ def reference_work_lists(tri, counts, nchunks, items_cap, max_dense=16):
             items, (kind == S.GROUP_SKIP).astype(np.uint8))
 
 
+def hex_lines_batch(total):
+    """One file of `total` bytes of lines of 32 hexadecimal digits, the last one cut short:
+    every chunk holds a class-U run, so the group of a rule like (?m)^[a-f0-9]{32}$ has items
+    in every chunk and wants K2's dense pass; every whole line is a match that a line start
+    (the file's for the first) and a line end decide."""
+    n = total // 33 + 1
+    text = b"".join(b"%032x\n" % (i * 0x9E3779B97F4A7C15F39CC0605CEDC835 % (1 << 128)) for i in range(1, n + 1))
+    from trivy_amd import secret as S
+    return S.Batch.from_args([S.ScanArgs("d/hex.txt", text[:total])])
+
+
 def dense_batch(chunk, total, long_tokens=False):
     """`total` bytes in which aws-access-key-id's group (gated by the keyword AKIA, no anchor:
     it listens to every chunk) and the first run-U group (keyword `key`, lines of long

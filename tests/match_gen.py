@@ -8,8 +8,13 @@ and, as a class of their own, the runes U+017F / U+212A that (?i) folds onto s /
 generator does not decide what matches: the oracle's FindAllIndex does, and a file in which
 it finds nothing is dropped (tests/test_candidate_cover.py).
 
+The context matrix (below) is the other way round: the string stays, the bytes around it
+change.  It is for empty-width assertions, and there the files without a match are kept.
+
 variants(src)          -> [(variant class, variant name, str)]
 files_for(rule, ...)   -> [GenFile]: the variants of one rule at their placements
+context_product(..)    -> [GenFile]: one core string between every before / after pair
+context_geometry(..)   -> [GenFile]: every single context on chunk, word and file boundaries
 """
 import random
 from dataclasses import dataclass
@@ -376,4 +381,65 @@ def files_for(rule_id, src, keywords, seed=0, reduced=True, only=None):
             for body, aux in place(s, keywords, pl):
                 fold = b"\xc5\xbf" in body or b"\xe2\x84\xaa" in body
                 out.append(GenFile(rule_id, cls, name, pl, body, fold, aux))
+    return out
+
+
+# ------------------------------------------------------------------------ context matrix
+# Empty-width assertions are decided by the bytes around a match, not by the match: one core
+# string per rule between every `before` and every `after` context.  "bot" / "eot": the core
+# begins / ends the file.
+BEFORE = (("bot", b""), ("nl", b"\n"), ("crlf", b"\r\n"), ("a", b"a"), ("_", b"_"), ("9", b"9"), ("sp", b" "),
+          ("comma", b","), ("e-acute", "é".encode()), ("ff", b"\xff"))
+AFTER = (("eot", b""), ("nl", b"\n"), ("crlf", b"\r\n"), ("cr", b"\r"), ("a", b"a"), ("_", b"_"), ("0", b"0"),
+         ("sp", b" "), ("comma", b","), ("e-acute", "é".encode()), ("ff", b"\xff"))
+# where a single context is put on the scan's geometry: the core starts on a 256-byte multiple
+# of the batch (its context byte is the previous chunk's last byte), ends on one (the
+# look-ahead byte is the next chunk's first), ends on a 16-byte word end that is no end of a
+# 64- or 256-byte chunk, and has a 256-byte multiple in its middle
+GEOMETRY = ("start256", "end256", "end16", "mid256")
+PAIR_AT = 100   # a file boundary in the middle of a chunk of 256 bytes, and of a 16-byte word
+
+
+def phase_of(gf):
+    """The offset modulo 256 of the batch at which a file wants to start (None: anywhere): 0
+    for the ALIGNED placements, the number behind '@' for a context file."""
+    if gf.placement in ALIGNED:
+        return 0
+    return int(gf.placement.split("@")[1]) if "@" in gf.placement else None
+
+
+def _ctx(rule_id, before, core, after, placement, at=None, aux=False):
+    body = before[1] + core + after[1]
+    if at is not None:
+        placement = "%s@%d" % (placement, at % 256)
+    return GenFile(rule_id, "ctx", before[0] + "|" + after[0], placement, body, False, aux)
+
+
+def context_product(rule_id, core):
+    """One file per (before, after) pair, wherever it falls in the batch."""
+    return [_ctx(rule_id, b, core, a, "product") for b in BEFORE for a in AFTER]
+
+
+def context_geometry(rule_id, core, before, after):
+    """Every single context at the four GEOMETRY placements -- each `before` with the partner
+    `after`, each `after` with the partner `before` -- and the file-boundary pairs: a file that
+    ends in a word character without a newline before one that begins with the core (the
+    file's start must win over the neighbour's byte), and a file that ends with the core
+    before one that begins with a word character (the file's end must win), each with the
+    boundary inside a chunk and on a 256-byte multiple of the batch."""
+    out = []
+    nc = len(core)
+    singles = [(b, after) for b in BEFORE] + [(before, a) for a in AFTER]
+    for b, a in singles:
+        nb = len(b[1])
+        for pl, at in (("start256", -nb), ("end256", -(nb + nc)), ("end16", 48 - (nb + nc)),
+                       ("mid256", -(nb + nc // 2))):
+            out.append(_ctx(rule_id, b, core, a, pl, at))
+    word = (("word", b"qz vxa"), ("", b""))
+    for pl, at in (("bot-pair", PAIR_AT), ("bot-pair256", 0)):
+        out.append(_ctx(rule_id, word[0], b"", word[1], pl, at - len(word[0][1]), aux=True))
+        out.append(_ctx(rule_id, BEFORE[0], core, after, pl))
+    for pl, at in (("eot-pair", PAIR_AT), ("eot-pair256", 0)):
+        out.append(_ctx(rule_id, before, core, AFTER[0], pl, at - len(before[1]) - nc))
+        out.append(GenFile(rule_id, "ctx", "|word", pl, b"a qz\n", False, True))
     return out

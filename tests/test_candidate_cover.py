@@ -4,10 +4,15 @@ decides what matches, K2's candidates (the emulation's records, expanded as the 
 expands them) must cover every true match, and the findings resolved from them must equal the
 exact path's and the oracle's.  The rule sets span every shape of GPU program the planner
 makes: each relaxation, prefix cuts with and without a suffix start, suffix programs, every
-anchor kind and host-only rules."""
+anchor kind and host-only rules.  Two sets keep their files without a match and pin the
+exact path to the oracle's match count per file: "assert" (every empty-width assertion
+between every pair of context bytes, on chunk, word and file boundaries) and "group64" (a
+group DFA of 64 rules)."""
 import ctypes as C
+import os
 import time
 
+import numpy as np
 import pytest
 
 from tests import cover_common as CC
@@ -76,6 +81,219 @@ def test_generator_variants_of_one_regex():
     assert all("K" not in s and "ſ" not in s for c, s in got if c != "fold")
     assert G.features(r"a[b-d]{2,}")["unbounded"] and not G.features(r"(?i)s[a-z]{2,5}")["nonascii"]
     assert G.features(r"[^a]")["nonascii"] and not G.features(r"a{2,5}")["unbounded"]
+
+
+# ------------------------------------------------- the context matrix and the full group
+def _edge_leaves(node, last):
+    """The leaves a match can begin with (last: end with), as node kinds."""
+    k = node[0]
+    if k == "cat":
+        return _edge_leaves(node[1][-1 if last else 0], last) if node[1] else set()
+    if k == "alt":
+        return set().union(*(_edge_leaves(x, last) for x in node[1]))
+    if k in ("group", "cap", "rep"):
+        return _edge_leaves(node[{"group": 1, "cap": 2, "rep": 4}[k]], last)
+    return {k}
+
+
+def _inner_assertions(node, inside_alt=False, out=None):
+    """(kind, "alt" | "between") of the assertions inside an alternation, and of those of a
+    concatenation that stand between two of its atoms."""
+    out = set() if out is None else out
+    k = node[0]
+    if k == "cat":
+        for i, x in enumerate(node[1]):
+            if x[0] in G._ASSERT and 0 < i < len(node[1]) - 1:
+                out.add((x[0], "between"))
+            _inner_assertions(x, inside_alt, out)
+    elif k == "alt":
+        for x in node[1]:
+            _inner_assertions(x, True, out)
+    elif k in ("group", "cap", "rep"):
+        _inner_assertions(node[{"group": 1, "cap": 2, "rep": 4}[k]], inside_alt, out)
+    elif k in G._ASSERT and inside_alt:
+        out.add((k, "alt"))
+    return out
+
+
+def _flagless(src):
+    while src.startswith("(?") and src[2] in "imsU" and ")" in src[:7] and ":" not in src[:src.index(")")]:
+        src = src[src.index(")") + 1:]
+    return src
+
+
+def test_assert_rules_hold_every_operation_plan_shape_and_table_layout():
+    """What makes the "assert" set worth having: all eight empty-width operations lead a rule
+    and end one (the parser has one node for ^ and \\A, and one for $ and \\z: those are told
+    apart by the source), \\b stands between atoms and a line anchor inside an alternation;
+    the plans hold literal, run-U and absent anchors, a suffix program, rules with and without
+    a reverse DFA and, under group_states 24, a relaxation of at most 2; and the device tables
+    (tsg_ruleset_group_table, the upload's own decision) are of both accept layouts."""
+    from oracle import goregex
+    lead, trail, inner = set(), set(), set()
+    for _, src, _, _ in CC.ASSERT_RULES:
+        ast = goregex.parse(src)
+        lead |= _edge_leaves(ast, False)
+        trail |= _edge_leaves(ast, True)
+        inner |= _inner_assertions(ast)
+    assert {"bot", "bol", "wb", "nwb"} <= lead, lead
+    assert {"eot", "eol", "wb", "nwb"} <= trail, trail
+    srcs = [_flagless(r[1]) for r in CC.ASSERT_RULES]
+    assert any(x.startswith("\\A") for x in srcs) and any(x.startswith("(?:^|") for x in srcs)
+    assert any(x.endswith("\\z") for x in srcs) and any(x.endswith("|$)") for x in srcs)
+    assert ("wb", "between") in inner and {("bol", "alt"), ("eot", "alt"), ("bot", "alt")} <= inner, inner
+    sc, own = CC.rule_set("assert")
+    assert sc.info()["n_hostonly"] == 0
+    assert {"anchor literal", "anchor run U", "anchor none", "suffix without a cut"} <= CC.shapes_of(sc, own)
+    assert {sc.rule_program(r)["rule_rev"] for r in own} == {True, False}
+    sc24, own24 = CC.rule_set(("assert", 24))
+    assert any(0 <= sc24.rule_plan(r)["relax"] <= 2 for r in own24), [CC.plan_line(sc24, r) for r in own24]
+    layouts = {}
+    for s, rules in ((sc, own), (sc24, own24)):
+        for g in {s.rule_group(r) for r in rules}:
+            layouts.setdefault(s.group_table(g)["per_state"], []).append(g)
+    assert set(layouts) == {True, False}, layouts
+    # a trailing assertion alone makes a table look-ahead: the rule without any is per-state
+    lzm = [r.ID for r in sc24.Rules].index("lzm")
+    t = sc24.group_table(sc24.rule_group(lzm))
+    assert t["rules"] == [lzm] and t["per_state"]
+    with pytest.raises(N.NativeError):
+        sc.group_table(sc.info()["n_groups"])
+    assert N.lib().tsg_ruleset_group_table(sc.handle, 0, None, None, None, 0) == 0
+
+
+def _product(cb, rule_id):
+    return {m.variant: bool(cb.truth[f]) for f, m in enumerate(cb.meta) if m.rule == rule_id and m.placement == "product"}
+
+
+def test_context_matrix_meets_its_conditions():
+    """The "assert" batch: per rule every (before, after) pair is a file, so every pair the
+    oracle admits is present and so is every pair it rejects; a rule whose first or last atom
+    is an assertion matches between some contexts and not between others, the two rules
+    whose match no context byte can touch (lzm: no assertion; wbn: both inside) between all;
+    the geometry files lie where their placement says; and a file's own start and end win
+    over the neighbour file's byte."""
+    from oracle import goregex
+    sc, own = CC.rule_set("assert")
+    cb = CC.cover_batch("assert")
+    pairs = {b[0] + "|" + a[0] for b in G.BEFORE for a in G.AFTER}
+    assert len(pairs) == 110 and len(own) == len(CC.ASSERT_RULES)
+    for rid, src, _, _ in CC.ASSERT_RULES:
+        got = _product(cb, rid)
+        assert set(got) == pairs, rid
+        ast = goregex.parse(src)
+        edge = (_edge_leaves(ast, False) | _edge_leaves(ast, True)) & set(G._ASSERT)
+        assert (set(got.values()) == {True, False}) if edge else all(got.values()), (rid, edge)
+    offs = cb.batch.offsets.astype(np.int64)
+    placements = set()
+    for f, m in enumerate(cb.meta):
+        pl = m.placement.split("@")[0]
+        placements.add(pl)
+        if "@" in m.placement:
+            assert offs[f] % 256 == G.phase_of(m), (f, m.placement)
+        if pl not in G.GEOMETRY:
+            continue
+        b, a = (dict(G.BEFORE)[m.variant.split("|")[0]], dict(G.AFTER)[m.variant.split("|")[1]])
+        core = CC.ASSERT_CORE[m.rule]
+        assert m.body == b + core + a
+        s0 = int(offs[f]) + len(b)
+        assert {"start256": s0 % 256 == 0, "end256": (s0 + len(core)) % 256 == 0,
+                "end16": (s0 + len(core)) % 16 == 0 and (s0 + len(core)) % 64 != 0,
+                "mid256": s0 // 256 < (s0 + len(core) - 1) // 256}[pl], (f, m.placement)
+    assert placements >= set(G.GEOMETRY) | {"product", "bot-pair", "bot-pair256", "eot-pair", "eot-pair256", "filler"}
+    # the pairs: the neighbour's last / first byte is a word character, next to the core
+    won = {"bot": set(), "eot": set()}
+    for f, m in enumerate(cb.meta):
+        pl = m.placement.split("@")[0]
+        if pl.startswith("bot-pair") and not m.aux:
+            assert cb.meta[f - 1].aux and cb.meta[f - 1].body.endswith(b"a") and m.body.startswith(CC.ASSERT_CORE[m.rule])
+            assert (offs[f] % 256 == 0) == (pl == "bot-pair256")
+            if cb.truth[f] and not _product(cb, m.rule)["a|" + m.variant.split("|")[1]]:
+                won["bot"].add((m.rule, pl))
+        if pl.startswith("eot-pair") and not m.aux:
+            assert cb.meta[f + 1].aux and cb.meta[f + 1].body.startswith(b"a") and m.body.endswith(CC.ASSERT_CORE[m.rule])
+            assert (offs[f + 1] % 256 == 0) == (pl == "eot-pair256")
+            if cb.truth[f] and not _product(cb, m.rule)[m.variant.split("|")[0] + "|a"]:
+                won["eot"].add((m.rule, pl))
+    # (rules that match at the file's edge and not beside the letter a)
+    assert {("wbd", "bot-pair"), ("wbd", "bot-pair256"), ("atg", "bot-pair"), ("mla", "bot-pair256")} <= won["bot"], won
+    assert {("wbe", "eot-pair"), ("wbe", "eot-pair256"), ("wbd", "eot-pair"), ("mlc", "eot-pair256")} <= won["eot"], won
+
+
+@pytest.mark.parametrize("name", ["assert", ("assert", 24), "group64"], ids=_id)
+def test_kept_batches_fit_the_default_capacities(name):
+    """The batches that keep their files without a match: under 2 MiB, the committed fixture
+    no larger than the largest one before them (builtin.json.gz, 96,632 bytes), no file
+    flagged, the reference under the default candidate capacity and no group skipped at the
+    default item capacity, at every chunk size the tests use."""
+    sc, _ = CC.rule_set(name)
+    cb = CC.cover_batch(name)
+    key = name if isinstance(name, str) else name[0]
+    assert int(cb.batch.offsets[-1]) < (2 << 20)
+    assert os.path.getsize(CC._fixture_path(key)) <= 96632
+    assert any(not t and not m.aux and m.placement != "filler" for m, t in zip(cb.meta, cb.truth))
+    for chunk in CC.CHUNKS + (48, 128):
+        n = H.nchunks_of(cb.batch, chunk)
+        ref = sc.emulate_candidates(cb.batch, chunk)
+        assert len(ref) < S.DEFAULT_CAND_CAPACITY
+        flags = H.reference_output(sc, cb.batch, chunk, ref)["flags"]
+        assert not (flags & 3).any()
+        _, counts = sc.emulate_items(cb.batch, chunk, 16)
+        kind, tot = S.layout_reference(counts, n, S.default_items_cap(n))
+        assert tot["skipped"] == 0
+        print("%s chunk %d: %d files, %d bytes, %d records, %s" % (_id(name), chunk, cb.batch.nfiles,
+                                                                     int(cb.batch.offsets[-1]), len(ref), tot))
+
+
+def _full_group(sc):
+    return next(g for g in range(sc.info()["n_groups"]) if len(sc.group_table(g)["rules"]) == 64)
+
+
+def test_group64_fills_a_group_and_reaches_every_mask_half():
+    """Some group has exactly max_rules_per_group = 64 rules, and the rules with local index
+    0, 31, 32 and 63 each have a candidate from an accepting transition and one from the
+    end-of-text mask; one 16-byte word of the batch holds the ends of two rules of the upper
+    half, and its word record expands to both.
+
+    The planner does NOT put the unbounded rule (?s)gqzz\\{.*\\} into the full group: its .*
+    state multiplies with the other rules' literal states, and listed first it leaves room for
+    38 others only.  It stays in the group of the seven rules behind the full one, whose
+    rules a tail in its immortal state returns whole, once each."""
+    sc, own = CC.rule_set("group64")
+    cb = CC.cover_batch("group64")
+    sizes = sorted(len(sc.group_table(g)["rules"]) for g in range(sc.info()["n_groups"]))
+    assert sizes == [1, 7, 64], sizes
+    g = _full_group(sc)
+    local = sc.group_table(g)["rules"]
+    unb = [r.ID for r in sc.Rules].index(CC.GROUP64_UNB)
+    assert unb not in local and len(sc.group_table(sc.rule_group(unb))["rules"]) == 7
+    size = np.diff(cb.batch.offsets.astype(np.int64))
+    for chunk in CC.CHUNKS:
+        ref = sc.emulate_candidates(cb.batch, chunk, word_recs=False)
+        trans = ref[(ref[:, 1] & S.CAND_TRANS) != 0]
+        assert not (trans[:, 1] & S.CAND_WORD).any()
+        plain = ref[((ref[:, 1] & S.CAND_TRANS) == 0) & (ref[:, 2] != S.CAND_WHOLE)]
+        assert (plain[:, 2] == size[plain[:, 0]]).all()           # the end-of-text emit alone
+        by_trans = set(sc.expand_candidates(cb.batch, trans)[:, 1].tolist())
+        by_eot = set(plain[:, 1].tolist())
+        for k in (0, 31, 32, 63):
+            assert local[k] in by_trans and local[k] in by_eot, (chunk, k)
+    # the two-ends file: both accepting transitions in one word of the batch
+    f = next(f for f, m in enumerate(cb.meta) if m.variant == "two-ends" and m.placement != "filler")
+    at = int(cb.batch.offsets[f])
+    assert at % 256 == 0
+    ref = sc.emulate_candidates(cb.batch, 128)   # (the full group is listed at this chunk size)
+    assert len(ref[ref[:, 0] == f]) == 1
+    words = ref[(ref[:, 0] == f) & ((ref[:, 1] & S.CAND_WORD) != 0)]
+    tri = sc.expand_candidates(cb.batch, words)
+    assert len(words) == 1 and sorted(tri[:, 2].tolist()) == [17, 27]
+    assert all(local.index(r) >= 32 for r in tri[:, 1].tolist()) and len(set(tri[:, 1].tolist())) == 2
+    assert (at + 17) // 16 == (at + 27) // 16
+    # the immortal tail: every rule of the unbounded rule's group whole, once
+    ref = sc.emulate_candidates(cb.batch, 16, ext_cap=256)
+    whole = ref[ref[:, 2] == S.CAND_WHOLE]
+    assert sorted(whole[:, 1].tolist()) == sorted(sc.group_table(sc.rule_group(unb))["rules"])
+    assert {cb.meta[f].variant for f in whole[:, 0].tolist()} == {"unbounded"}
 
 
 # ------------------------------------------------------------------------------ the plans
@@ -156,6 +374,7 @@ def test_committed_batches_are_current(key):
 def test_findings_from_candidates_equal_the_exact_path(name, chunk):
     sc, _ = CC.rule_set(name)
     cb = CC.cover_batch(name)
+    key = name if isinstance(name, str) else name[0]
     want = sc.ScanBatch(cb.batch, nthreads=16)
     got = sc.ScanBatch(cb.batch, emulate_chunk=chunk)
     for f in range(cb.batch.nfiles):
@@ -168,6 +387,10 @@ def test_findings_from_candidates_equal_the_exact_path(name, chunk):
         ru = sc.Rules[cb.rule[f]]
         if found and not (ru.AllowRules or ru.Path or ru.ExcludeBlock.Regexes or sc.AllowRules):
             assert any(x["RuleID"] == ru.ID for x in want[f]["Findings"] or []), (f, ru.ID)
+            # ... as often as the oracle matches it -- in a batch that keeps its files without a
+            # match that is no finding where the oracle has none: exact == oracle in both directions
+        if (found or key in CC.KEEP_UNMATCHED) and not (ru.AllowRules or ru.Path or ru.ExcludeBlock.Regexes or sc.AllowRules):
+            assert sum(x["RuleID"] == ru.ID for x in want[f]["Findings"] or []) == len(found), (f, ru.ID, cb.meta[f].variant)
 
 
 @pytest.mark.slow

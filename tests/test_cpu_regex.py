@@ -134,3 +134,41 @@ def test_builtin_rules_vs_oracle_random(rules, samples):
         finally:
             N.lib().tsg_regex_free(h)
     assert nmatch > 10
+
+
+def test_assertion_contexts_engines_agree_and_equal_the_oracle():
+    """Every file of the "assert" batch (tests/cover_common.py: one core string of a rule with
+    an empty-width assertion between every pair of context bytes, \\B, \\A and \\z among them)
+    under the file's rule: the Pike VM and the backtracker agree with and without submatches,
+    and the default engine equals the oracle's FindAllSubmatchIndex."""
+    from oracle.goregex import MustCompile
+    from tests import cover_common as CC
+    sc, _ = CC.rule_set("assert")
+    cb = CC.fixture_batch("assert")
+    per = {}
+    for f, m in enumerate(cb.meta):
+        per.setdefault(cb.rule[f], set()).add(m.body)
+    nmatch = ntext = 0
+    matched = set()
+    for r, texts in sorted(per.items()):
+        src = sc.Rules[r].Regex
+        o = MustCompile(src)
+        h = compile_re(src)
+        try:
+            for t in sorted(texts):
+                idx = find_all(h, t, False, 1)
+                sub = find_all(h, t, True, 1)
+                assert find_all(h, t, False, 2) == idx and find_all(h, t, True, 2) == sub, (src, t)
+                want = [(-1 if x is None else x) for m in o.FindAllSubmatchIndex(t) for x in m]
+                assert find_all(h, t, True, 0) == want == sub, (src, t)
+                nmatch += len(idx) > 0
+                ntext += 1
+                if idx:
+                    matched.add(r)
+        finally:
+            N.lib().tsg_regex_free(h)
+    print("%d texts, %d with a match" % (ntext, nmatch))
+    # every rule at every context pair (distinct texts), each with a match somewhere, and
+    # most texts without one
+    assert ntext >= 110 * len(CC.ASSERT_RULES) and len(matched) == len(per) == len(CC.ASSERT_RULES)
+    assert nmatch < ntext // 2

@@ -193,6 +193,14 @@ def test_k2_records_capped(cap, kernel):
     assert st["k2_dense_entries"] == 2 * -(-H.nchunks_of(batch, chunk) // S.ENTRY_CHUNKS)
 
 
+def test_assertion_contexts_capped(cap):
+    """The "assert" batch of tests/cover_common.py (look-ahead tables, every start row, the
+    end-of-text emit) with the entries claimed by one block and by three."""
+    batch, want = k2_exact("assert", ("cover", "assert"))
+    st, nref, _ = run_records(k2_scanner_for("assert", "default"), batch, want, 256, rich="either")
+    assert nref > 1000 and st["k2_launches"] > 1 and st["k2_dense_entries"] > 0
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_k2_overflow_records_capped(cap, kernel):
     sc = k2_scanner_for("builtin", kernel)

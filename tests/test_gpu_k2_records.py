@@ -87,6 +87,35 @@ def test_dense_records(chunk, total, ext_cap, long_tokens, kernel, words):
 
 @WORDS
 @pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("rules", ["assert", "group64"])
+def test_assertion_contexts_and_a_full_group(rules, kernel, words):
+    """The committed batches of tests/cover_common.py at chunk 128: every empty-width assertion
+    between every pair of context bytes and on the scan's geometry, files without a match kept
+    (four start rows, look-ahead tables, the end-of-text emit), and a group DFA of 64 rules
+    (accept-mask bits 32..63).  (Their tables are small: the device's occupancy query picks
+    the list kernel under either setting.)"""
+    sc = _scanner(rules, kernel)
+    batch, want = _exact(rules, ("cover", rules))
+    st, nref, _ = _run(sc, batch, want, 128, kernel, words, rich="either")
+    print("%s, %s: %d records, k2_rich %d" % (rules, kernel, nref, st["k2_rich"]))
+    assert nref > 100 and st["groups_skipped"] == 0
+
+
+@WORDS
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("chunk,total", H.DENSE_SHAPES)
+def test_line_anchored_rule_through_the_dense_kernel(chunk, total, kernel, words):
+    """k2_dense_kernel on a look-ahead table: a file of 32-hex-digit lines sends the group of
+    (?m)^[a-f0-9]{32}$ through the dense pass (tests/test_k2_paths.py proves that on the CPU),
+    where every line start and line end is decided across lane ranges and chunk segments."""
+    sc = _scanner("assert", kernel)
+    batch, want = _exact("assert", ("hex lines", total))
+    st, nref, _ = _run(sc, batch, want, chunk, kernel, words, rich="either")
+    assert st["k2_dense_entries"] > 0 and nref >= total // 33
+
+
+@WORDS
+@pytest.mark.parametrize("kernel", KERNELS)
 def test_many_groups(kernel, words):
     """Seeded corpora: 128 KiB under 1,000 user rules (many small groups) and the 256 KiB
     corpus under the builtin rules, where words with several accepting transitions make the

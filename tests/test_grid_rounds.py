@@ -8,6 +8,7 @@ the last round is partial -- and K2's persistent loop gets the entry sequences i
 import numpy as np
 import pytest
 
+from tests import cover_common as CC
 from tests import device_layer_common as XL
 from tests import device_spans_common as XS
 from tests import grid_rounds_common as R
@@ -134,6 +135,7 @@ def test_k2_entry_sequences(builtin, user):
         "entry shapes": (k2, H.entry_shape_batch(*R.ENTRY_SHAPE)[0], R.ENTRY_SHAPE[0]),
         "dense": (builtin, H.dense_batch(*H.DENSE_SHAPES[0])[0], H.DENSE_SHAPES[0][0]),
         "user items": (user, R.user_items_batch(), R.ROUNDS_CHUNK),
+        "assertion contexts": (CC.rule_set("assert")[0], CC.fixture_batch("assert").batch, 256),
     }
     seen = {}
     for name, (sc, batch, chunk) in inputs.items():

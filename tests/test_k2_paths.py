@@ -441,6 +441,37 @@ def test_dense_reference_and_whole_file_records(builtin, chunk, total):
         assert ends and all(whole[(ff, r)] == len(ends) for r in rules), (ff, ends, whole)
 
 
+@pytest.mark.parametrize("chunk,total", H.DENSE_SHAPES)
+def test_hex_lines_batch_sends_a_look_ahead_table_through_the_dense_pass(chunk, total):
+    """The file of 32-hex-digit lines under the "assert" rules of tests/cover_common.py: the
+    group of (?m)^[a-f0-9]{32}$ (anchor: a class-U run, which every chunk holds) has an item in
+    more than half of the chunks and gets the dense pass, its device table is look-ahead (the
+    trailing (?m)$), every whole line is a finding and nothing else is, the reference stays
+    under the default candidate capacity and both record forms expand alike."""
+    from oracle import goregex
+    from tests import cover_common as CC
+    sc, _ = CC.rule_set("assert")
+    batch = H.hex_lines_batch(total)
+    n = H.nchunks_of(batch, chunk)
+    assert batch.nfiles == 1 and int(batch.offsets[-1]) == total and total % 33
+    r = [x.ID for x in sc.Rules].index("hex32")
+    g = sc.rule_group(r)
+    assert sc.group_table(g) == {"rules": [r], "per_state": False}
+    assert CC.plan_of(sc, r)["kind"] == "run U"
+    _, counts = sc.emulate_items(batch, chunk, 16)
+    kind, tot = S.layout_reference(counts, n, S.default_items_cap(n))
+    assert counts[g] * 2 > n and kind[g] == S.GROUP_DENSE and tot["skipped"] == 0
+    ref, named = _reference(sc, batch, chunk)
+    lines = [(0, "hex32", 33 * i + 32) for i in range(total // 33)]
+    assert [t for t in named if t[1] == "hex32"] == lines
+    want = sc.ScanBatch(batch, nthreads=8)
+    assert sum(f["RuleID"] == "hex32" for f in want[0]["Findings"]) == len(lines)
+    if chunk == 16:   # (the oracle on the smaller shape: the lines are what it finds)
+        body = bytes(batch.data[:total])
+        assert [e for _, e in goregex.MustCompile(sc.Rules[r].Regex).FindAllIndex(body)] == [t[2] for t in lines]
+    assert sc.ScanBatch(batch, emulate_chunk=chunk) == want
+
+
 def test_many_group_inputs_fit_the_default_capacity(builtin, corpus256k):
     """The seeded corpora of the record tests: under the default capacity, word and
     transition forms agree, and on the 256 KiB corpus the word form is the shorter one and

@@ -27,8 +27,9 @@ for g in CC.GROUP_STATES:
     CASES[CC.set_id(("builtin", g))] = ("builtin", {} if g is None else {"group_states": g})
 CASES["builtin-table32"] = ("builtin", {"group_table_kib": 32})
 CASES["builtin-1024-table48"] = ("builtin", {"group_states": 1024, "group_table_kib": 48})
-for name in ("blob", "foldcut", "k2", "hostonly", "user40"):
-    CASES[name] = (name, {})
+COVER_SETS = ("blob", "foldcut", "k2", "hostonly", "user40", "assert", ("assert", 24), "group64")
+for name in COVER_SETS:
+    CASES[CC.set_id(name)] = (name, {})
 CASES["user100"] = ("user100", {})
 CASES["user100-no_k1x"] = ("user100", {"no_k1x": 1})
 CASES["user1000"] = ("user1000", {})
@@ -40,7 +41,7 @@ CASES["allow-exclude"] = ("allow-exclude", {})
 
 def compile_case(case):
     rules, knobs = CASES[case]
-    if rules in ("blob", "foldcut", "k2", "hostonly", "user40"):
+    if rules in COVER_SETS:
         return CC.rule_set(rules)[0]   # (they set their own knobs, and are shared with other tests)
     doc = {"builtin": lambda: None, "user100": lambda: configs.user_rules_doc(100, seed=4),
            "user1000": lambda: configs.user_rules_doc(1000, seed=4),

@@ -224,6 +224,8 @@ SIGNATURES = [
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     ("tsg_ruleset_rule_program", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("tsg_ruleset_group_table", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_uint32), C.c_uint32]),
     ("tsg_emulate_k1", C.c_int, [_P, _P, _U64P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                  C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
     ("tsg_layer_pack", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32,

@@ -6,6 +6,7 @@
 #include <exception>
 #include <thread>
 
+#include "dfa_layout.hpp"
 #include "internal.hpp"
 #include "k1f.hpp"
 
@@ -466,6 +467,16 @@ int tsg_ruleset_rule_program(const tsg_ruleset* rs, uint32_t rule, int32_t* firs
   if (rule_atoms) *rule_atoms = p.rule_atoms[rule];
   if (winback) *winback = p.rule_winback[rule];
   if (has_rev) *has_rev = p.rule_rev[rule] ? 1 : 0;
+  return TSG_OK;
+}
+
+int tsg_ruleset_group_table(const tsg_ruleset* rs, uint32_t group, uint32_t* nrules, int32_t* per_state,
+                            uint32_t* rules, uint32_t cap) {
+  if (!rs || group >= rs->plan->groups.size() || (!rules && cap)) return fail(TSG_ERR_ARG, "bad argument");
+  const GroupPlan& g = rs->plan->groups[group];
+  if (nrules) *nrules = (uint32_t)g.rules.size();
+  if (per_state) *per_state = (int32_t)dev_dfa_layout(*g.dfa).state_acc;
+  for (size_t k = 0; k < g.rules.size() && k < cap; k++) rules[k] = g.rules[k];
   return TSG_OK;
 }
 

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "dfa_layout.hpp"
 #include "internal.hpp"
 #include "k1f.hpp"
 
@@ -2832,8 +2833,6 @@ static int upload_vec(const std::vector<T>& v, P** dst, std::vector<void*>* allo
   return TSG_OK;
 }
 
-static uint32_t align16(uint32_t x) { return (x + 15) & ~15u; }
-
 static int make_device_dfa(const DFA& dd, const std::vector<uint32_t>& rules, DevDFA* out,
                            std::vector<void*>* allocs) {
   if (dd.nstates >= 0x8000) return fail(TSG_ERR_INTERNAL, "DFA too large for u16 tables");
@@ -2857,7 +2856,6 @@ static int make_device_dfa(const DFA& dd, const std::vector<uint32_t>& rules, De
   const DFA& d = *dp;
   const size_t nc = d.nclasses;
   std::vector<uint16_t> tab((size_t)d.nstates * nc), acc(tab.size()), accs(d.nstates, 0);
-  bool state_acc = true;
   if ((size_t)(d.nstates - 1) * nc >= 0x8000) return fail(TSG_ERR_INTERNAL, "DFA rows do not fit 15 bits");
   for (int s = 0; s < d.nstates; s++) {
     uint32_t a0 = d.acc[(size_t)s * nc];
@@ -2866,7 +2864,6 @@ static int make_device_dfa(const DFA& dd, const std::vector<uint32_t>& rules, De
       if (d.acc[i] > 0xFFFF) return fail(TSG_ERR_INTERNAL, "too many accept masks");
       tab[i] = (uint16_t)((d.next[i] * nc) | (d.acc[i] ? 0x8000u : 0u));
       acc[i] = (uint16_t)d.acc[i];
-      if (d.acc[i] != a0) state_acc = false;
     }
     accs[s] = (uint16_t)a0;
   }
@@ -2900,22 +2897,14 @@ static int make_device_dfa(const DFA& dd, const std::vector<uint32_t>& rules, De
   v.nmasks = (uint32_t)d.masks.size();
   for (int k = 0; k < 4; k++) v.start[k] = d.start[k] * (uint32_t)nc;
   v.inv_nc = (uint32_t)((0x100000000ull + nc - 1) / nc);
-  // LDS layout
-  uint32_t o = align16((uint32_t)(tab.size() * 2));
-  v.o_cls = o;
-  o += 256;
-  v.o_dead = o;  // the tails' per-word liveness test reads it
-  o += align16((uint32_t)d.nstates);
-  v.o_accs = o;
-  v.o_masks = o;
-  v.state_acc = 0;
-  const uint32_t acc_bytes = align16(d.nstates * 2) + align16((uint32_t)masks.size() * 8);
-  if (state_acc && o + acc_bytes + 16 * 1024 <= 150 * 1024) {
-    v.state_acc = 1;
-    v.o_masks = o + align16(d.nstates * 2);
-    o += acc_bytes;
-  }
-  v.lds_bytes = o + 16;
+  // LDS layout and the accept layout: dev_dfa_layout's decision (dfa_layout.hpp)
+  const DevDfaLayout lay = dev_dfa_layout(d);
+  v.o_cls = lay.o_cls;
+  v.o_dead = lay.o_dead;
+  v.o_accs = lay.o_accs;
+  v.o_masks = lay.o_masks;
+  v.state_acc = lay.state_acc;
+  v.lds_bytes = lay.lds_bytes;
   if (v.lds_bytes > 160 * 1024) return fail(TSG_ERR_INTERNAL, "DFA tables exceed LDS");
   return TSG_OK;
 }

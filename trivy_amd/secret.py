@@ -397,6 +397,16 @@ class Scanner:
         return {"first_atom": fa.value, "rule_atoms": at.value, "rule_winback": wb.value,
                 "rule_rev": bool(rev.value)}
 
+    def group_table(self, group):
+        """Test hook (tsg_ruleset_group_table): K2 group `group`'s rules in local order (a
+        rule's position is its bit in the group's accept masks) and the accept layout of its
+        device table, as the upload decides it: per_state True (accepts per state, staged in
+        LDS) or False (look-ahead: accepts per transition)."""
+        n, ps = C.c_uint32(), C.c_int32()
+        rules = (C.c_uint32 * 64)()
+        N.check(N.lib().tsg_ruleset_group_table(self.handle, group, C.byref(n), C.byref(ps), rules, 64))
+        return {"rules": list(rules[:n.value]), "per_state": bool(ps.value)}
+
     def k1_literals(self):
         """K1's literals as (bytes, event bits); ids below n_keywords are keywords."""
         out = []
