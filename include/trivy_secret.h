@@ -285,6 +285,20 @@ int tsg_test_adaptation(tsg_ctx* ctx, tsg_adaptation_info* info, uint8_t* kw_unk
                         uint8_t* event_everywhere, size_t event_everywhere_len, uint32_t* hits,
                         size_t hits_len, uint8_t* quiet, size_t quiet_len);
 
+/* Test hook: the HBM buffers of the context's lanes.  A batch runs on one lane, in that lane's
+ * buffers, which grow on demand and otherwise still hold the lane's previous batch; a test
+ * that means to run a batch on used memory reads this before and after it.  Read-only and
+ * synchronous, under the context lock; host values only (no device call); TSG_ERR_ARG on an
+ * emulated context.  n[0..2] = lanes, buffers per lane, and the lane the last batch was
+ * enqueued on (by any entry point; 0xFFFFFFFF before the first).  Up to bufs_cap records are
+ * written (bufs may be NULL), lane by lane, each lane's buffers in the same order. */
+typedef struct tsg_lane_buffer {
+  char name[24];   /* the member's name in LaneState, NUL-terminated: "kw", "ev_bits", ... */
+  uint64_t bytes;  /* capacity in bytes (0: never allocated) */
+  uint64_t allocs; /* allocations so far: unchanged since an earlier call = same memory */
+} tsg_lane_buffer;
+int tsg_test_lane_buffers(tsg_ctx* ctx, tsg_lane_buffer* bufs, size_t bufs_cap, uint32_t* n);
+
 typedef struct tsg_stats {
   double k1_ms;          /* K1 literal automaton + run counters, last collected batch (HIP events) */
   double k2_ms;          /* K2 rule-group DFAs (the persistent work-list launch) */

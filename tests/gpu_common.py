@@ -1,5 +1,8 @@
-"""Harnesses shared by the device tests: one batch on a fresh context, compared exactly with
-the CPU references.  They were the private helpers of tests/test_gpu_configs.py,
+"""Harnesses shared by the device tests: one batch compared exactly with the CPU references.
+Each comparison is a function that takes the context (k1_on, lists_on, records_on, and
+check_batch, which runs all of them on one kernels() call) and a wrapper that opens a fresh
+context for it; tests/test_gpu_lane_reuse.py runs the former on contexts that other batches
+have used.  They were the private helpers of tests/test_gpu_configs.py,
 tests/test_gpu_k2_paths.py and tests/test_gpu_k2_records.py, which import them from here, as
 does tests/test_gpu_grid_rounds.py (the same comparisons under the knob grid_cap)."""
 import functools
@@ -16,20 +19,30 @@ NEVER = 0xFFFFFFFF
 
 
 # ---- K1 (+ K1X) bits and events
+def k1_on(sc, ctx, b, ref=None):
+    """upload + kernels() of batch b on the context ctx: K1 (+ K1X) keyword bits and chunk
+    events == k1_reference at the context's chunk (ref: that reference, where the caller has
+    it).  Returns (keyword bits, events, stats)."""
+    import numpy as np
+    ctx.upload(b)
+    ctx.kernels()
+    kw, ev = ctx.k1_output(ctx.chunk)
+    st = ctx.stats()
+    rkw, rev = ref if ref is not None else sc.k1_reference(b, ctx.chunk)
+    assert np.array_equal(kw, rkw)
+    assert np.array_equal(ev, rev)
+    return kw, ev, st
+
+
 def k1_vs_reference(sc, b, chunks=(64, 256)):
     """K1 (+ K1X) keyword bits and chunk events of batch b == k1_reference, on a fresh context
     per chunk size.  Returns the stats of the last one."""
-    import numpy as np
     for chunk in chunks:
         ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, adapt_mib=0xFFFFFFFF)
-        ctx.upload(b)
-        ctx.kernels()
-        kw, ev = ctx.k1_output(chunk)
-        st = ctx.stats()
-        ctx.close()
-        rkw, rev = sc.k1_reference(b, chunk)
-        assert np.array_equal(kw, rkw)
-        assert np.array_equal(ev, rev)
+        try:
+            st = k1_on(sc, ctx, b)[2]
+        finally:
+            ctx.close()
     return st
 
 
@@ -57,16 +70,22 @@ def dense_case(chunk, total):
     return batch, plants, tri, counts, H.nchunks_of(batch, chunk), sc.ScanBatch(batch, nthreads=16)
 
 
+def lists_on(ctx, batch):
+    """upload + kernels() of one batch on the context ctx: (work lists, stats)."""
+    ctx.upload(batch)
+    ctx.kernels()
+    return ctx.batch_items(), ctx.stats()
+
+
 def run_lists(sc, batch, chunk, **kw):
     """kernels() + work lists + stats + findings of one batch on a fresh context."""
     ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, adapt_mib=NEVER, **kw)
-    ctx.upload(batch)
-    ctx.kernels()
-    st = ctx.stats()
-    lists = ctx.batch_items()
-    got = ctx.scan()
-    st2 = ctx.stats()
-    ctx.close()
+    try:
+        lists, st = lists_on(ctx, batch)
+        got = ctx.scan()
+        st2 = ctx.stats()
+    finally:
+        ctx.close()
     return lists, st, got, st2
 
 
@@ -125,6 +144,39 @@ def k2_exact(rules, key):
     return batch, sc.ScanBatch(batch, nthreads=16)
 
 
+def compare_records(sc, batch, chunk, st, dev, ext_cap, cand_cap, items_cap=None, words=True, counts=None, ref=None):
+    """What batch_candidates() read back (dev) and the stats of its kernels() call (st) against
+    emulate_candidates under the given settings (check_candidates), with the stats candidates,
+    groups_skipped and overflow.  counts / ref: emulate_items' counts and emulate_candidates'
+    records, where the caller has them.  Returns (reference records, expanded triples)."""
+    n = H.nchunks_of(batch, chunk)
+    items_cap = S.default_items_cap(n) if items_cap is None else items_cap
+    if ref is None:
+        ref = sc.emulate_candidates(batch, chunk, ext_cap, word_recs=words, items_cap=items_cap)
+    if counts is None:
+        _, counts = sc.emulate_items(batch, chunk, 16)
+    skipped = S.layout_reference(counts, n, items_cap)[1]["skipped"]
+    assert dev["cand_cap"] == cand_cap
+    nref, ntri = H.check_candidates(dev, ref, batch, sc, chunk, skipped=skipped > 0)
+    assert st["candidates"] == nref and st["groups_skipped"] == skipped
+    assert st["overflow"] == (1 if nref > dev["cand_cap"] else 0)
+    return nref, ntri
+
+
+def records_on(sc, ctx, batch, words=True, items_cap=None, dev_out=None):
+    """upload + kernels() -> batch_candidates() -> compare_records with the context's own
+    chunk, ext_cap and cand_capacity.  Returns (stats, reference records, expanded triples)."""
+    assert ctx.ext_cap is not None and ctx.cand_capacity is not None, "a context that does not know its options"
+    ctx.upload(batch)
+    ctx.kernels()
+    st = ctx.stats()
+    dev = ctx.batch_candidates()
+    nref, ntri = compare_records(sc, batch, ctx.chunk, st, dev, ctx.ext_cap, ctx.cand_capacity, items_cap, words)
+    if dev_out is not None:
+        dev_out.update(dev)
+    return st, nref, ntri
+
+
 def run_records(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0, cand_capacity=0, rich=None,
                 items_cap=None, dev_out=None):
     """kernels() -> batch_candidates() -> check_candidates against emulate_candidates with the
@@ -136,23 +188,9 @@ def run_records(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0,
     Returns (stats of kernels(), reference records, reference triples)."""
     ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, ext_cap=ext_cap, cand_capacity=cand_capacity, adapt_mib=NEVER)
     try:
-        ctx.upload(batch)
-        ctx.kernels()
-        st = ctx.stats()
-        dev = ctx.batch_candidates()
-        n = H.nchunks_of(batch, chunk)
-        items_cap = S.default_items_cap(n) if items_cap is None else items_cap
-        ref = sc.emulate_candidates(batch, chunk, ext_cap or S.DEFAULT_EXT_CAP, word_recs=words, items_cap=items_cap)
-        _, counts = sc.emulate_items(batch, chunk, 16)
-        skipped = S.layout_reference(counts, n, items_cap)[1]["skipped"]
-        assert dev["cand_cap"] == (cand_capacity or S.DEFAULT_CAND_CAPACITY)
-        nref, ntri = H.check_candidates(dev, ref, batch, sc, chunk, skipped=skipped > 0)
-        assert st["candidates"] == nref and st["groups_skipped"] == skipped
-        assert st["overflow"] == (1 if nref > dev["cand_cap"] else 0)
+        st, nref, ntri = records_on(sc, ctx, batch, words, items_cap, dev_out)
         if rich != "either":
             assert st["k2_rich"] == ((0 if kernel == "small tables" else 1) if rich is None else rich), st["k2_rich"]
-        if dev_out is not None:
-            dev_out.update(dev)
         got = ctx.scan()
         with pytest.raises(N.NativeError):  # something was submitted since kernels()
             ctx.batch_candidates()
@@ -160,3 +198,111 @@ def run_records(sc, batch, want, chunk, kernel="default", words=True, ext_cap=0,
         ctx.close()
     assert got == want
     return st, nref, ntri
+
+
+# ---- all of it on one kernels() call of a context that may have run other batches before
+class BatchRef:
+    """The CPU references of one batch under one set of context settings, each computed when
+    first asked for and then kept (a sequence runs the same batch on several contexts)."""
+
+    def __init__(self, sc, batch, chunk, ext_cap=0, items_cap=None, max_dense=16, words=True):
+        self.sc, self.batch, self.chunk = sc, batch, chunk
+        self.ext_cap = ext_cap or S.DEFAULT_EXT_CAP
+        self.n = H.nchunks_of(batch, chunk)
+        self.items_cap = S.default_items_cap(self.n) if items_cap is None else items_cap
+        self.max_dense, self.words = max_dense, words
+
+    @functools.cached_property
+    def k1(self):
+        return self.sc.k1_reference(self.batch, self.chunk)
+
+    @functools.cached_property
+    def items(self):
+        return self.sc.emulate_items(self.batch, self.chunk, 16)
+
+    @functools.cached_property
+    def layout(self):
+        return S.layout_reference(self.items[1], self.n, self.items_cap, self.max_dense)
+
+    @functools.cached_property
+    def records(self):
+        return self.sc.emulate_candidates(self.batch, self.chunk, self.ext_cap, items_cap=self.items_cap,
+                                          max_dense=self.max_dense, word_recs=self.words)
+
+    @functools.cached_property
+    def exact(self):
+        return self.sc.ScanBatch(self.batch, nthreads=16)
+
+    @functools.cached_property
+    def event_chunks(self):
+        import numpy as np
+        return int(np.count_nonzero(self.k1[1] & 0x7FFFFFFF))
+
+
+def read_batch(ctx, batch, upload=None):
+    """upload + one kernels() call + everything the test hooks read back of it.  upload(ctx,
+    batch): another way into a slot the context then holds, in place of ctx.upload."""
+    if upload is None:
+        ctx.upload(batch)
+    else:
+        upload(ctx, batch)
+    ctx.kernels()
+    kw, ev = ctx.k1_output(ctx.chunk)
+    return {"kw": kw, "ev": ev, "stats": ctx.stats(), "lists": ctx.batch_items(), "cand": ctx.batch_candidates()}
+
+
+def _sorted_records(r):
+    import numpy as np
+    r = np.asarray(r, dtype=np.uint32).reshape(-1, 3)
+    return r[np.lexsort((r[:, 2], r[:, 1], r[:, 0]))]
+
+
+def compare_batch(ref, rb, cand_cap):
+    """One kernels() call's readback rb (read_batch) against the references ref (BatchRef),
+    everything exactly:
+      K1 (+ K1X) keyword bits and events == k1_reference;
+      entries, dense entries, items and gskip == emulate_items + layout_reference
+        (check_work_lists), with the stats k2_items, k2_launches, k2_dense_entries,
+        groups_skipped; event_chunks == the reference's chunks with an event;
+      records, flags and rows == emulate_candidates (check_candidates), with the stats
+        candidates, overflow, groups_skipped; without an overflow also the records as a sorted
+        array, every flag and every row == reference_output (under an overflow the device
+        chooses which records it drops: check_candidates' containment is the whole claim).
+    Returns the layout's totals."""
+    import numpy as np
+    sc, batch, chunk = ref.sc, ref.batch, ref.chunk
+    st, dev = rb["stats"], rb["cand"]
+    assert np.array_equal(rb["kw"], ref.k1[0]), "keyword bits differ in files %s" % (
+        np.flatnonzero((rb["kw"] != ref.k1[0]).any(axis=1))[:8].tolist())
+    assert rb["ev"].shape == ref.k1[1].shape
+    assert np.array_equal(rb["ev"], ref.k1[1]), "events differ in chunks %s" % (
+        np.flatnonzero(rb["ev"] != ref.k1[1])[:8].tolist())
+    tri, counts = ref.items
+    kind, tot = H.check_work_lists(rb["lists"], tri, counts, ref.n, ref.items_cap, ref.max_dense)
+    check_stats(st, tot)
+    assert tot == ref.layout[1]
+    assert st["event_chunks"] == ref.event_chunks, (st["event_chunks"], ref.event_chunks)
+    nref, _ = compare_records(sc, batch, chunk, st, dev, ref.ext_cap, cand_cap, ref.items_cap, ref.words,
+                              counts=counts, ref=ref.records)
+    if nref <= cand_cap:
+        out = H.reference_output(sc, batch, chunk, ref.records, cand_cap, skipped=tot["skipped"] > 0)
+        assert np.array_equal(_sorted_records(dev["records"]), _sorted_records(out["records"]))
+        assert np.array_equal(dev["flags"], out["flags"]), np.flatnonzero(dev["flags"] != out["flags"])[:8].tolist()
+        assert np.array_equal(dev["kw"], out["kw"])
+    return tot
+
+
+def check_batch(sc, ctx, batch, ref=None, items_cap=None, upload=None):
+    """Batch `batch` through one kernels() call of the context ctx, whatever ran on it before,
+    and compare_batch of its readback with the context's own chunk_bytes, ext_cap and
+    cand_capacity and the k2_items_cap knob current for this batch (items_cap; None: unset).
+    upload: see read_batch.
+    Returns (readback, layout totals)."""
+    assert ctx.ext_cap is not None and ctx.cand_capacity is not None, "a context that does not know its options"
+    if ref is None:
+        ref = BatchRef(sc, batch, ctx.chunk, ctx.ext_cap, items_cap)
+    assert (ref.chunk, ref.ext_cap) == (ctx.chunk, ctx.ext_cap) and ref.batch is batch
+    assert ref.items_cap == (S.default_items_cap(ref.n) if items_cap is None else items_cap)
+    rb = read_batch(ctx, batch, upload)
+    tot = compare_batch(ref, rb, ctx.cand_capacity)
+    return rb, tot

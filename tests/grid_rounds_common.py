@@ -70,6 +70,19 @@ def k1x_batch(total):
     return trimmed(args, total)
 
 
+@functools.lru_cache(maxsize=None)
+def k1x_overflow_case():
+    """(scanner, batch) of tests/test_gpu_configs.py's test_k1x_list_overflow_inline_verify: the
+    1,000 user rules and a periodic literal, and a 2 MiB batch every 16-byte word of which holds
+    that literal, so that the blocks' list slices overflow and k1x_kernel verifies inline."""
+    doc = configs.user_rules_doc(1000, seed=4)
+    doc["rules"].append({"id": "periodic", "category": "user", "title": "periodic", "severity": "LOW",
+                         "regex": r"qzqzqzqzqz(?P<secret>[0-9]{4})", "keywords": ["qzqzqzqzqz"]})
+    sc = S.NewScanner(S.config_from_dict(doc))
+    files = [S.ScanArgs("p/%d.txt" % i, b"qz" * (16 << 10) + b"0123\n") for i in range(64)]
+    return sc, S.Batch.from_args(files)
+
+
 # ---- compaction, item passes and K2: a corpus of 65,555 chunks of 16 bytes, dense with events
 ROUNDS_CHUNK = 16
 

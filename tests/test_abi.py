@@ -25,7 +25,7 @@ def test_header_declares_the_boundary():
     for n in ["tsg_ruleset_compile", "tsg_ruleset_allow_path", "tsg_scan_cpu", "tsg_scan_batch",
               "tsg_ctx_create", "tsg_batch_upload", "tsg_slot_submit", "tsg_batch_collect",
               "tsg_multi_create", "tsg_multi_scan_batch", "tsg_result_data", "tsg_result_free",
-              "tsg_last_error"]:
+              "tsg_last_error", "tsg_test_lane_buffers"]:
         assert n in names
 
 

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests import k1_adapted_common as AC
 from trivy_amd import configs
 from trivy_amd import corpus
 from trivy_amd import secret as S
@@ -28,75 +29,8 @@ K1S = ("k1f", "automaton")
 FOLD = pytest.mark.parametrize("fold_hot", [True, False], ids=["fold hot", "fold rare"])
 
 
-@functools.lru_cache(maxsize=None)
-def _scanner():
-    return S.NewScanner(None)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(fold_hot):
-    """(batch, picks, plain counts per literal, predicted quiet set) of an adapting batch."""
-    sc = _scanner()
-    batch, picks = H.adapted_batch(sc, fold_hot=fold_hot)
-    counts = H.literal_counts(sc, batch)
-    nkw = sc.info()["n_keywords"]
-    quiet, tied = H.predict_quiet(counts, int(batch.offsets[-1]), set(range(nkw - 3, nkw)))
-    assert not tied
-    return batch, picks, counts, quiet
-
-
-@functools.lru_cache(maxsize=None)
-def _big_case():
-    return H.adapted_batch(_scanner(), H.ADAPT_BIG_TOTAL)[0]
-
-
-@functools.lru_cache(maxsize=None)
-def _item_case(fold_hot, chunk):
-    """The unadapted references of an adapting batch: item triples and counts, the per-item
-    candidate triples, the exact findings."""
-    sc = _scanner()
-    batch = _case(fold_hot)[0]
-    tri, counts = sc.emulate_items(batch, chunk, 16)
-    return tri, counts, sc.emulate_item_candidates(batch, chunk), sc.ScanBatch(batch, nthreads=16)
-
-
-def _adapted_context(sc, batch, chunk=0):
-    """A context with adapt_mib = 1 after kernels() of the adapting batch."""
-    ctx = S.GpuContext(sc, 0, chunk_bytes=chunk, adapt_mib=1)
-    ctx.upload(batch)
-    ctx.kernels()
-    return ctx
-
-
-def _kw_mask(nkw, W, ids):
-    m = np.zeros(W, dtype=np.uint32)
-    for k in ids:
-        if k < nkw:
-            m[k // 32] |= np.uint32(1 << (k % 32))
-    return m
-
-
-def _check_bits(sc, ctx, batch, chunk, a, scanned=False):
-    """K1's output for `batch` on the adapted context against the references: outside the
-    unknown keywords and the hot event classes it equals k1_reference, inside it is a subset;
-    K1F's equals k1f_emulate without the quiet literals exactly, its quiet columns are zero."""
-    if not scanned:
-        ctx.upload(batch)
-        ctx.kernels()
-    kw, ev = ctx.k1_output(chunk)
-    rkw, rev = sc.k1_reference(batch, chunk)
-    nkw = sc.info()["n_keywords"]
-    unknown = _kw_mask(nkw, kw.shape[1], np.flatnonzero(a["kw_unknown"]).tolist())
-    hot = np.uint32(a["ev_hot"])
-    assert np.array_equal(kw & ~unknown, rkw & ~unknown)
-    assert np.array_equal(ev & ~hot, rev & ~hot)
-    assert not (kw & ~rkw).any() and not (ev & ~rev).any()
-    if a["k1_filter"]:
-        assert not (kw & unknown).any()
-        if not sc.info()["k1x_literals"]:  # (the emulation is K1F's alone: no K1X bits)
-            fk, fe, _ = sc.k1f_emulate(batch, chunk, np.flatnonzero(a["quiet"]).tolist())
-            assert np.array_equal(kw, fk)
-            assert np.array_equal(ev, fe)
+_scanner, _case, _big_case, _item_case = AC.scanner, AC.case, AC.big_case, AC.item_case
+_adapted_context, _check_bits = AC.adapted_context, AC.check_bits
 
 
 @FOLD
@@ -205,10 +139,6 @@ def test_batch_larger_than_the_sample(knob, k1):
         ctx.close()
 
 
-def _rows(a):
-    return set(map(tuple, np.asarray(a, dtype=np.int64).reshape(-1, 2).tolist()))
-
-
 @FOLD
 @pytest.mark.parametrize("chunk", [16, 256])
 def test_gates_items_and_k2_after_adaptation(chunk, fold_hot):
@@ -221,71 +151,12 @@ def test_gates_items_and_k2_after_adaptation(chunk, fold_hot):
     try:
         st, a = ctx.stats(), ctx.adaptation()
         kw_dev, _ = ctx.k1_output(chunk)
-        ent, dent, items, gskip = lists = ctx.batch_items()
+        lists = ctx.batch_items()
         dev = ctx.batch_candidates()
         got = ctx.scan()
     finally:
         ctx.close()
-    G, F = sc.info()["n_groups"], batch.nfiles
-    n = H.nchunks_of(batch, chunk)
-    offs = batch.offsets.astype(np.int64)
-    nonempty = offs[1:] > offs[:-1]
-    first, last = offs[:-1] // chunk, (offs[1:] - 1) // chunk
-    every = {(f, c) for f in np.flatnonzero(nonempty).tolist() for c in range(int(first[f]), int(last[f]) + 1)}
-    gate0, evw0 = H.gates_after_adaptation(sc, np.zeros(len(a["kw_unknown"]), np.uint8), 0)
-    touched = (a["gate_open"] != gate0) | (a["event_everywhere"] != evw0)
-    assert touched.any() and not gskip.any()
-    # the device's items per group, gathered through its list entries
-    dev_items = {g: np.concatenate([items[int(s):int(s) + int(m)] for _, s, m, _ in ent[ent[:, 0] == g]])
-                 for g in set(ent[:, 0].tolist())}
-    dense = set(dent[:, 0].tolist())
-    dev_counts = np.zeros(G, dtype=np.uint64)
-    dev_tri = [tri[~touched[tri[:, 0]]]]
-    opened = 0
-    for g in range(G):
-        ref = _rows(tri[tri[:, 0] == g][:, 1:])
-        if not touched[g]:
-            dev_counts[g] = counts[g]      # (check_work_lists compares its items with the reference's)
-            continue
-        full = bool(a["gate_open"][g] and a["event_everywhere"][g])
-        opened += full
-        if g in dense:
-            # a touched group takes the dense pass over every chunk: its count is known only
-            # where it must hold every chunk of every non-empty file
-            assert full and g not in dev_items, g
-            dev_counts[g] = len(every)
-            continue
-        arr = dev_items.get(g, np.zeros((0, 2), dtype=np.uint32)).astype(np.int64)
-        rows = _rows(arr)
-        assert len(rows) == len(arr), "group %d: an item twice" % g
-        f, c = arr[:, 0], arr[:, 1]
-        assert (f < F).all() and nonempty[f].all() and (first[f] <= c).all() and (c <= last[f]).all(), g
-        assert ref <= rows, (g, sorted(ref - rows)[:4])
-        if full:
-            assert rows == every, g
-        dev_counts[g] = len(arr)
-        dev_tri.append(np.column_stack([np.full(len(arr), g), arr]).astype(tri.dtype))
-    assert opened > 0
-    # layout and tiling of the device's lists from its own counts; untouched groups' items exact
-    kind, tot = H.check_work_lists(lists, np.concatenate(dev_tri), dev_counts, n, S.default_items_cap(n))
-    assert (st["k2_items"], st["k2_launches"], st["k2_dense_entries"], st["groups_skipped"]) == (
-        tot["items"], tot["entries"], tot["dense_entries"], tot["skipped"])
-    for g in dense:
-        assert kind[g] == S.GROUP_DENSE
-    # K2's records
-    assert dev["count"] <= dev["cand_cap"]
-    got_tri = sc.expand_candidates(batch, dev["records"])
-    group = np.array([sc.rule_group(r) for r in range(len(sc.Rules))])
-    assert (group >= 0).all()
-    as_set = lambda t: set(map(tuple, np.asarray(t, dtype=np.int64).reshape(-1, 3).tolist()))
-    untouched_rule = ~touched[group]
-    assert as_set(got_tri[untouched_rule[got_tri[:, 1]]]) == as_set(cand_ref[untouched_rule[cand_ref[:, 1]]])
-    missing = as_set(cand_ref) - as_set(got_tri)
-    assert not missing, sorted(missing)[:4]
-    if not fold_hot:
-        assert untouched_rule[cand_ref[:, 1]].any() and (~untouched_rule[cand_ref[:, 1]]).any()
-    rows = (dev["flags"] & 4) != 0
-    assert rows.any() and np.array_equal(dev["kw"][rows], kw_dev[rows])
+    AC.check_lists_and_records(sc, batch, chunk, a, st, kw_dev, lists, dev, tri, counts, cand_ref, mixed=not fold_hot)
     # a file whose only keyword is a quiet one is still resolved
     assert got == want
     found_a, found_b, _ = H.adapted_findings(sc, batch, picks, got)

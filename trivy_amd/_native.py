@@ -99,6 +99,11 @@ class AdaptationInfo(C.Structure):
                 ("n_groups", C.c_uint32), ("n_literals", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LaneBuffer(C.Structure):
+    """tsg_lane_buffer, in the header's order."""
+    _fields_ = [("name", C.c_char * 24), ("bytes", C.c_uint64), ("allocs", C.c_uint64)]
+
+
 class DeviceInputStats(C.Structure):
     """tsg_device_input_stats, in the header's order."""
     _fields_ = [("stage_ms", C.c_double), ("fetch_ms", C.c_double),
@@ -163,6 +168,7 @@ SIGNATURES = [
                                        C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U64P]),
     ("tsg_test_adaptation", C.c_int, [_P, C.POINTER(AdaptationInfo), _U8P, C.c_size_t, _U8P, C.c_size_t,
                                       _U8P, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U8P, C.c_size_t]),
+    ("tsg_test_lane_buffers", C.c_int, [_P, C.POINTER(LaneBuffer), C.c_size_t, C.POINTER(C.c_uint32)]),
     ("tsg_batch_collect", C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),

@@ -204,6 +204,14 @@ struct LaneItems {
   uint64_t extent = 0;  // the layout's extent (counter kCntItems)
 };
 int lane_items(LaneState* l, LaneItems* out);
+// Every DevBuf member of the lane by name, with its capacity in bytes and the allocations it
+// has had (test hook, tsg_test_lane_buffers): host values only, no device call.  A batch
+// that found `allocs` as the previous batch on the lane left it ran in that batch's memory.
+struct LaneBuffer {
+  const char* name;
+  uint64_t bytes, allocs;
+};
+void lane_buffers(const LaneState* l, std::vector<LaneBuffer>* out);
 // K2 per-entry trace of the lane's last batch (TSG_K2_TRACE; empty otherwise): per entry
 // {start, end, group << 32 | items, XCC_ID << 32 | HW_ID}
 int lane_k2_trace(LaneState* l, std::vector<unsigned long long>* out);

@@ -3122,6 +3122,7 @@ template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  uint64_t allocs = 0;  // allocations so far (test hook lane_buffers: unchanged = the buffer was reused)
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
@@ -3139,8 +3140,10 @@ struct DevBuf {
     const size_t alloc = exact ? n : std::max<size_t>(n + n / 8, 16);
     HIP_TRY(hipMalloc((void**)&p, exact ? alloc * sizeof(T) : (alloc * sizeof(T) + 15) & ~(size_t)15));
     cap = alloc;
+    allocs++;
     return TSG_OK;
   }
+  size_t bytes() const { return cap * sizeof(T); }
 };
 
 // ---------------------------------------------------------------- rule tables on a device
@@ -4166,6 +4169,35 @@ int lane_items(LaneState* l, LaneItems* out) {
   if (ni) HIP_TRY(hipMemcpy(out->items.data(), l->items, sizeof(uint2) * ni, hipMemcpyDeviceToHost));
   if (G) HIP_TRY(hipMemcpy(out->gskip.data(), l->gskip, G, hipMemcpyDeviceToHost));
   return TSG_OK;
+}
+
+void lane_buffers(const LaneState* l, std::vector<LaneBuffer>* out) {
+  out->clear();
+#define TSG_LANE_BUF(m) out->push_back(LaneBuffer{#m, l->m.bytes(), l->m.allocs})
+  TSG_LANE_BUF(data_alloc);
+  TSG_LANE_BUF(meta);
+  TSG_LANE_BUF(cf);
+  TSG_LANE_BUF(ev_bits);
+  TSG_LANE_BUF(xlist);
+  TSG_LANE_BUF(xcount);
+  TSG_LANE_BUF(evlist);
+  TSG_LANE_BUF(zclaim);
+  TSG_LANE_BUF(wtrace);
+  TSG_LANE_BUF(kw);
+  TSG_LANE_BUF(ggate);
+  TSG_LANE_BUF(ovf);
+  TSG_LANE_BUF(hascand);
+  TSG_LANE_BUF(items);
+  TSG_LANE_BUF(entries);
+  TSG_LANE_BUF(dentries);
+  TSG_LANE_BUF(cand);
+  TSG_LANE_BUF(counts);
+  TSG_LANE_BUF(gcount);
+  TSG_LANE_BUF(bcount);
+  TSG_LANE_BUF(cursor);
+  TSG_LANE_BUF(gskip);
+  TSG_LANE_BUF(etrace);
+#undef TSG_LANE_BUF
 }
 
 int lane_events(LaneState* l, uint32_t* ev, size_t n) {

@@ -145,6 +145,7 @@ struct tsg_ctx {
   DeviceRules* dr = nullptr;
   std::vector<LaneState*> lanes;
   uint64_t seq = 0;
+  int last_lane = -1;  // the lane of the last enqueued batch (tsg_test_lane_buffers)
   std::vector<std::unique_ptr<Slot>> slots;
   std::vector<HostOut> outs;
   std::vector<char> out_busy;
@@ -630,7 +631,8 @@ int submit_locked(tsg_ctx* c, uint32_t sid, uint32_t nfiles, bool keep_result,
   std::shared_ptr<const std::vector<uint8_t>> kwu;
   if (!c->emulate && !(d.spans && nfiles == 0)) {  // (no launch for a spans batch without a kept file)
     if ((rc = out_take(c, nfiles, &b->out))) return rc;
-    LaneState* l = c->lanes[c->seq++ % c->lanes.size()];
+    c->last_lane = (int)(c->seq++ % c->lanes.size());
+    LaneState* l = c->lanes[c->last_lane];
     ScanInput in = slot_input(s, nfiles);
     if (d.on()) {  // the content comes from the caller's HBM; the slot's is fetched later
       in = ScanInput{d.spans ? ScanSource::kHbmSpans : ScanSource::kPackedHbm, s.off, nfiles, s.off[nfiles]};
@@ -1391,7 +1393,8 @@ int tsg_batch_kernels(tsg_ctx* c, uint32_t slot_id, uint32_t nfiles, uint32_t* k
     }
     int oi;
     if ((rc = out_take(c, nfiles, &oi))) return rc;
-    LaneState* l = c->lanes[c->seq++ % c->lanes.size()];
+    c->last_lane = (int)(c->seq++ % c->lanes.size());
+    LaneState* l = c->lanes[c->last_lane];
     const ScanInput in = slot_input(s, nfiles);
     if ((rc = enqueue_scan(c->dr, l, in, &c->outs[oi]))) {
       c->out_busy[oi] = 0;
@@ -1485,6 +1488,35 @@ int tsg_batch_candidates(tsg_ctx* c, uint32_t slot_id, uint32_t* records, size_t
         if (ho.ovf[f] & 4) std::memcpy(kw + (size_t)f * W, ho.kw + (size_t)f * W, sizeof(uint32_t) * W);
         else std::memset(kw + (size_t)f * W, 0, sizeof(uint32_t) * W);
       }
+    return TSG_OK;
+  });
+}
+
+int tsg_test_lane_buffers(tsg_ctx* c, tsg_lane_buffer* bufs, size_t bufs_cap, uint32_t* n) {
+  if (!c || !n) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    // (the context lock, as tsg_batch_items: no batch is enqueued, so no buffer grows, meanwhile)
+    std::lock_guard<std::mutex> g(c->m);
+    if (c->emulate) return fail(TSG_ERR_ARG, "an emulated context has no lanes");
+    std::vector<LaneBuffer> v;
+    size_t k = 0;
+    n[0] = (uint32_t)c->lanes.size();
+    n[1] = 0;
+    n[2] = c->last_lane < 0 ? 0xFFFFFFFFu : (uint32_t)c->last_lane;
+    for (const LaneState* l : c->lanes) {
+      lane_buffers(l, &v);
+      n[1] = (uint32_t)v.size();
+      for (const LaneBuffer& b : v) {
+        if (bufs && k < bufs_cap) {
+          tsg_lane_buffer& o = bufs[k];
+          std::memset(&o, 0, sizeof(o));
+          std::strncpy(o.name, b.name, sizeof(o.name) - 1);
+          o.bytes = b.bytes;
+          o.allocs = b.allocs;
+        }
+        k++;
+      }
+    }
     return TSG_OK;
   });
 }

@@ -566,6 +566,8 @@ class GpuContext:
         self._owned = True
         self.scanner = scanner
         self.chunk = chunk_bytes or 256
+        self.ext_cap = ext_cap or DEFAULT_EXT_CAP                    # (tsg_ctx_options' defaults)
+        self.cand_capacity = cand_capacity or DEFAULT_CAND_CAPACITY
         opt = N.CtxOptions(chunk_bytes, ext_cap, cand_capacity, host_threads, adapt_mib,
                            N.TSG_CTX_EMULATE if emulate else 0, slot_mib, max_slots)
         h = C.c_void_p()
@@ -591,6 +593,7 @@ class GpuContext:
         self._owned = False
         self.scanner = scanner
         self.chunk = chunk_bytes or 256
+        self.ext_cap = self.cand_capacity = None   # (the owner's options: not known here)
         self._upload = None
         self._k1 = None
         self._lock = threading.Lock()
@@ -694,6 +697,20 @@ class GpuContext:
                 "sample_bytes": int(info.sample_bytes), "kw_unknown": kwu[:nk], "gate_open": gate[:ng],
                 "event_everywhere": evw[:ng], "hits": hits[:nl] if nl else None,
                 "quiet": quiet[:nl] if nl else None}
+
+    def lane_buffers(self):
+        """The HBM buffers of the context's lanes (tsg_test_lane_buffers): ([{name: (bytes,
+        allocs)} per lane], the lane the last batch was enqueued on or None).  allocs
+        unchanged between two calls: the batches in between ran in the same memory."""
+        n = (C.c_uint32 * 3)()
+        N.check(N.lib().tsg_test_lane_buffers(self._h, None, 0, n))
+        bufs = (N.LaneBuffer * max(n[0] * n[1], 1))()
+        m = (C.c_uint32 * 3)()
+        N.check(N.lib().tsg_test_lane_buffers(self._h, bufs, n[0] * n[1], m))
+        assert list(m) == list(n)
+        lanes = [{bufs[k * n[1] + i].name.decode(): (int(bufs[k * n[1] + i].bytes), int(bufs[k * n[1] + i].allocs))
+                  for i in range(n[1])} for k in range(n[0])]
+        return lanes, (None if n[2] == 0xFFFFFFFF else int(n[2]))
 
     def k1_output(self, chunk):
         """(keyword bits [nfiles, kw_words], chunk event bits) of the last kernels() call."""
