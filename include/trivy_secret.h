@@ -299,6 +299,37 @@ typedef struct tsg_lane_buffer {
 } tsg_lane_buffer;
 int tsg_test_lane_buffers(tsg_ctx* ctx, tsg_lane_buffer* bufs, size_t bufs_cap, uint32_t* n);
 
+/* Test hook: the layout of the automaton K1 (k1_kernel), which has two bodies.  Packed: rows
+ * as 16-bit byte offsets, states x stride x 2 <= 65,536 bytes, a 128 KiB LDS image.  Legacy:
+ * rows as entry indices, anything larger, a 156 KiB image with the class words replicated per
+ * lane.  Host values only, no device call. */
+typedef struct tsg_k1_layout {
+  uint32_t packed;        /* 1 = packed, 0 = legacy */
+  uint32_t states;        /* states of the keyword automaton (tsg_ruleset_info.kw_states) */
+  uint32_t classes;       /* its byte classes (tsg_ruleset_info.kw_classes) */
+  uint32_t stride;        /* u16 entries per row: the class count, padded to 2 mod 4 where that
+                             neither changes the layout nor overflows the rows */
+  uint32_t row_unit;      /* row of state id = id * row_unit (packed: stride * 2, bytes;
+                             legacy: stride, entries) */
+  uint32_t table_bytes;   /* the transition table as staged into LDS (whole dwords) */
+  uint32_t lds_class;     /* legacy: LDS size class of the image, 0..2 (52, 80, 156 KiB) */
+  uint32_t rep;           /* legacy: 1 = the class words are replicated per lane */
+  uint32_t lds_kib;       /* the kernel's static LDS image, KiB */
+  uint32_t threads;       /* its block size, 0 = no kernel is built for this layout */
+  uint32_t blocks_per_cu; /* resident blocks per CU of its persistent grid */
+  uint32_t kw_words;      /* tsg_test_k1_layout: 32-bit words of a keyword row */
+  uint32_t k1_filter;     /* tsg_test_k1_layout: 1 = batches under 4 GiB run K1F instead */
+  uint32_t reserved;
+} tsg_k1_layout;
+/* The layout an automaton of `states` x `classes` gets: pure arithmetic.  TSG_ERR_ARG where
+ * device tables cannot be made of it: states = 0, classes = 0 or > 128, rows past 16 bits, a
+ * table past LDS, or a layout no kernel is built for (out is filled all the same then). */
+int tsg_test_k1_layout_of(uint32_t states, uint32_t classes, tsg_k1_layout* out);
+/* The same record read from the context's device tables (they keep their layout through the
+ * K1 adaptation), with kw_words and k1_filter.  Under the context lock; TSG_ERR_ARG on an
+ * emulated context. */
+int tsg_test_k1_layout(tsg_ctx* ctx, tsg_k1_layout* out);
+
 typedef struct tsg_stats {
   double k1_ms;          /* K1 literal automaton + run counters, last collected batch (HIP events) */
   double k2_ms;          /* K2 rule-group DFAs (the persistent work-list launch) */

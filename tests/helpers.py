@@ -62,6 +62,39 @@ def small_files_batch(seed):
     return S.Batch.from_args(args)
 
 
+RUN_U = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/=_.-"   # run class U
+RUN_D = b"0123456789-"                                                            # run class D
+RUN_LENGTHS = (11, 12, 13, 31, 32, 33, 254, 255, 256, 257, 65534, 65535, 65536, 65537, 70000)
+RUN_PADS = (0, 1, 15, 16, 17)
+
+
+def run_saturation_batch(seed=5):
+    """K1's run counters at and past saturation: runs of class-U bytes and of class-D bytes of
+    every length in RUN_LENGTHS (around the rules' thresholds, around 255 and 256, where a
+    counter of 8 bits ends, and around 65,535 and 65,536, where one of 16 bits does), each in
+    a file of its own behind 0, 1, 15, 16 or 17 spaces (the run starts at every kind of
+    offset in a 16-byte word) and ended by a newline, since K1 counts over the batch as one
+    byte stream; then a run of 300 + 300 digits split over two files, and a run of 66,000
+    class-U bytes that ends at the batch's last byte.  153 files, 3.4 MB.  A counter that
+    wraps where it should saturate loses the event of every chunk that lies inside a run
+    behind the wrap."""
+    import numpy as np
+    from trivy_amd import secret as S
+    rng = np.random.default_rng(seed)
+
+    def run(alphabet, n):
+        return bytes(np.frombuffer(alphabet, dtype=np.uint8)[rng.integers(0, len(alphabet), n)])
+    files = []
+    for alphabet in (RUN_U, RUN_D):
+        for n in RUN_LENGTHS:
+            for pad in RUN_PADS:
+                files.append(b" " * pad + run(alphabet, n) + b"\n")
+    files.append(b"x " + run(b"0123456789", 300))
+    files.append(run(b"0123456789", 300) + b" y\n")
+    files.append(run(RUN_U, 66000))
+    return S.Batch.from_args([S.ScanArgs("r/%d.txt" % i, c) for i, c in enumerate(files)])
+
+
 def group_table(sc, chunk):
     """Per K2 group of scanner sc: (event bits, back window in chunks), from the plan's
     per-rule anchors (a group listens to the OR of its rules' events, as far back as its

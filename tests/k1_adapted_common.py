@@ -17,9 +17,10 @@ def scanner():
 
 
 @functools.lru_cache(maxsize=None)
-def case(fold_hot):
-    """(batch, picks, plain counts per literal, predicted quiet set) of an adapting batch."""
-    sc = scanner()
+def case(fold_hot, sc=None):
+    """(batch, picks, plain counts per literal, predicted quiet set) of an adapting batch for
+    the scanner sc (default: the builtin rules')."""
+    sc = scanner() if sc is None else sc
     batch, picks = H.adapted_batch(sc, fold_hot=fold_hot)
     counts = H.literal_counts(sc, batch)
     nkw = sc.info()["n_keywords"]

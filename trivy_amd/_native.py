@@ -104,6 +104,13 @@ class LaneBuffer(C.Structure):
     _fields_ = [("name", C.c_char * 24), ("bytes", C.c_uint64), ("allocs", C.c_uint64)]
 
 
+class K1Layout(C.Structure):
+    """tsg_k1_layout, in the header's order."""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "packed", "states", "classes", "stride", "row_unit", "table_bytes", "lds_class", "rep",
+        "lds_kib", "threads", "blocks_per_cu", "kw_words", "k1_filter", "reserved")]
+
+
 class DeviceInputStats(C.Structure):
     """tsg_device_input_stats, in the header's order."""
     _fields_ = [("stage_ms", C.c_double), ("fetch_ms", C.c_double),
@@ -169,6 +176,8 @@ SIGNATURES = [
     ("tsg_test_adaptation", C.c_int, [_P, C.POINTER(AdaptationInfo), _U8P, C.c_size_t, _U8P, C.c_size_t,
                                       _U8P, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, _U8P, C.c_size_t]),
     ("tsg_test_lane_buffers", C.c_int, [_P, C.POINTER(LaneBuffer), C.c_size_t, C.POINTER(C.c_uint32)]),
+    ("tsg_test_k1_layout_of", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(K1Layout)]),
+    ("tsg_test_k1_layout", C.c_int, [_P, C.POINTER(K1Layout)]),
     ("tsg_batch_collect", C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
     ("tsg_batch_pending", C.c_int, [_P]),
     ("tsg_scan_batch", C.c_int, [_P, _P, _U64P, C.c_uint32, _P, _U64P, C.POINTER(_P)]),

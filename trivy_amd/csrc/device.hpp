@@ -172,6 +172,17 @@ struct AdaptationView {
 int device_rules_adaptation(const DeviceRules* d, AdaptationView* out);
 // true: K1 runs as K1F (k1f_kernel, batches under 4 GiB); false: the automaton (k1_kernel)
 bool device_rules_k1_filter(const DeviceRules* d);
+// The automaton K1's layout (test hooks tsg_test_k1_layout_of / tsg_test_k1_layout): host
+// values only, no device call.  threads = 0: no kernel is built for the layout.
+struct K1LayoutView {
+  uint32_t packed = 0, states = 0, classes = 0, stride = 0, row_unit = 0, table_bytes = 0;
+  uint32_t lds_class = 0, rep = 0, lds_kib = 0, threads = 0, blocks_per_cu = 0, kw_words = 0;
+};
+// the layout make_device_k1 gives an automaton of ns states and nc classes; TSG_ERR_ARG
+// where it (or k1_tables) fails, `out` filled as far as the arithmetic goes
+int k1_layout_of(uint32_t ns, uint32_t nc, K1LayoutView* out);
+// the same read from the device tables (classes: the plan's)
+void device_rules_k1_layout(const DeviceRules* d, K1LayoutView* out);
 // true: K2's list pass runs k2_kernel_rich (decided by the occupancy API), false: k2_kernel
 bool device_rules_k2_rich(const DeviceRules* d);
 // bytes of K1X's verify image (staged in LDS up to kXImgLds), 0 without K1X

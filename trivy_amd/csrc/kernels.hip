@@ -52,13 +52,15 @@ constexpr int kStreams = 4;  // K2 dense: chunks per lane
 constexpr int kK1Chains = 2;  // K1: chains per lane (independent dependent-LDS chains)
 constexpr int kK1Unroll = 8;  // K1: bytes of a word unrolled (8 of 16: profiles/r04/k1g, 0.394 ms against 0.420 for 16)
 constexpr int kK1Seg = 8;     // K1: consecutive chunks per chain
-// legacy K1 layout: static LDS size classes (KiB): 3, 2 or 1 blocks per CU, of 512, 512
-// and 1024 threads (16 waves per CU at 4 per SIMD, whose registers bound a lane)
+// legacy K1 layout: LDS size classes (KiB) of the image, as k1_lds_class sorts a table.  A
+// legacy table is larger than 64 KiB (else it is packed) and at most 96 KiB (the plan's
+// max_kw_table_bytes), so with its replicated class words it always lands in the last class:
+// one kernel is built, for that class, of 1024 threads and 1 block per CU (16 waves per CU
+// at 4 per SIMD, whose registers bound a lane); tests/test_k1_layout.py sweeps the arithmetic
 constexpr int kK1Lds[3] = {52, 80, 156};
-constexpr int kK1BlocksPerCU[3] = {3, 2, 1};
-constexpr __host__ __device__ int k1_threads(int ldsk) { return ldsk == 156 ? 1024 : 512; }
+constexpr int kK1LLdsK = kK1Lds[2];
 // legacy class words replicated per lane of a 32-lane half ([byte][lane & 31] words: every
-// lane reads its own bank) when the automaton leaves room for it; else 256 words
+// lane reads its own bank)
 constexpr uint32_t kK1RepBytes = 256 * 32 * 4;
 constexpr int kBlock = 256;
 constexpr int kPad = 256;     // zero bytes before and after the batch in HBM (>= K1 warm-up)
@@ -582,8 +584,9 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // 8-byte aligned: 
 // contiguous bytes, conflict-free), 64 KiB; the transitions follow at kK1PTab.
 //
 // Legacy (automata too large for 16-bit byte offsets, e.g. a large user rule set): class
-// words (class * 2 | 0xFF00 if in D | 0xFFFF0000 if in U), replicated per lane where the
-// automaton leaves room (K1_REP), the transition table after them, rows as entry indices.
+// words (class * 2 | 0xFF00 if in D | 0xFFFF0000 if in U), replicated per lane (K1_REP: a
+// table under the plan's cap always leaves room), the transition table after them, rows as
+// entry indices.  These two bodies are the only ones built (k1_fn).
 constexpr uint32_t kK1PTab = 256 * 256;  // packed: class entries below, transitions above
 constexpr int kK1PLdsK = 128;            // packed: static LDS image, KiB (1 block of 1024 per CU)
 
@@ -693,7 +696,9 @@ __device__ __forceinline__ void k1_accept(const DevK1& d, const K1Args& A, uint3
   }
 }
 
-template <int KWW, bool PACKED, bool REP>
+// (REP is true in both bodies that are built, see k1_fn: the `REP ? ... : ...` alternatives
+// below and in k1_kernel are the replicated class words everywhere)
+template <bool PACKED, bool REP>
 struct K1Lane {
   const DevK1& d;
   const K1Args& A;
@@ -854,7 +859,7 @@ struct K1Lane {
 // The K1 kernel: every block stages the automaton once (a persistent grid), then its quads
 // walk 4 consecutive items together (uniform trip count inside a quad).  Accept masks stay
 // in global memory (rare path).  LDSK: the static LDS image in KiB.
-template <int KWW, bool PACKED, int LDSK, bool REP, int TPB>
+template <bool PACKED, int LDSK, bool REP, int TPB>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 8))) k1_kernel(DevK1 d, K1Args A) {
   constexpr int NS = kK1Chains;
   __shared__ __attribute__((aligned(16))) uint8_t smem[LDSK * 1024];
@@ -876,7 +881,7 @@ __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 8))
   }
   __syncthreads();
   const uint32_t lane = threadIdx.x & 31;
-  K1Lane<KWW, PACKED, REP> L{d, A, smem, smem + (REP ? kK1RepBytes : 1024), (const uint32_t*)smem + (REP ? lane : 0),
+  K1Lane<PACKED, REP> L{d, A, smem, smem + (REP ? kK1RepBytes : 1024), (const uint32_t*)smem + (REP ? lane : 0),
                              lane * 8};
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   const uint32_t q = threadIdx.x & 3;
@@ -2929,6 +2934,10 @@ static int k1_lds_class(size_t tab_bytes) {
 // the packed layout holds rows as 16-bit byte offsets: ns * stride u16 entries in 64 KiB
 static bool k1_packed_fits(size_t ns, size_t rs) { return ns * rs * 2 <= 65536; }
 
+// The two K1 bodies that are built (k1_fn): the packed one, and the legacy one of the last
+// LDS class with replicated class words.  No table the plan accepts gets another layout.
+static bool k1_has_kernel(bool packed, uint32_t lds_class, uint32_t rep) { return packed || (lds_class == 2 && rep == 1); }
+
 // Row stride (u16 entries) of the K1 table: the class count padded to 2 mod 4, so a row is
 // an odd number of dwords and equal classes of different rows fall in different LDS banks
 // (ds_read_u16 banks are dword mod 32).  Padding is skipped when it would change the
@@ -3114,6 +3123,8 @@ static int make_device_k1(const Plan& p, DevK1* out, std::vector<void*>* allocs,
   v.lds_class = (uint32_t)(lc >> 1);
   v.rep = (uint32_t)(lc & 1);
   if (!v.packed && v.lds_class > 2) return fail(TSG_ERR_INTERNAL, "keyword automaton exceeds LDS");
+  if (!k1_has_kernel(v.packed, v.lds_class, v.rep))
+    return fail(TSG_ERR_INTERNAL, "no K1 kernel is built for the keyword automaton's layout");
   return TSG_OK;
 }
 
@@ -3240,38 +3251,59 @@ struct LaneState {
   }
 };
 
-template <bool PACKED, int LDSK, bool REP, int TPB>
-static const void* k1_fn_w(uint32_t kw_words) {
-  if (kw_words <= 1) return (const void*)k1_kernel<1, PACKED, LDSK, REP, TPB>;
-  if (kw_words <= 2) return (const void*)k1_kernel<2, PACKED, LDSK, REP, TPB>;
-  if (kw_words <= 4) return (const void*)k1_kernel<4, PACKED, LDSK, REP, TPB>;
-  return (const void*)k1_kernel<8, PACKED, LDSK, REP, TPB>;
+// the kernel of a layout (make_device_k1 lets no other layout through: k1_has_kernel); both
+// run 1024 threads, 1 block per CU
+constexpr int kK1Threads = 1024, kK1BlocksPerCU = 1;
+static const void* k1_fn(const DevK1& k) {
+  if (k.packed) return (const void*)k1_kernel<true, kK1PLdsK, true, kK1Threads>;
+  return (const void*)k1_kernel<false, kK1LLdsK, true, kK1Threads>;
 }
 
-// the kernel of a layout and its block size / blocks per CU
-static const void* k1_fn(const DevK1& k, int* threads, int* per_cu) {
-  if (k.packed) {
-    *threads = 1024;
-    *per_cu = 1;
-    return k1_fn_w<true, kK1PLdsK, true, 1024>(k.kw_words);
-  }
-  const uint32_t lc = std::min<uint32_t>(k.lds_class, 2);
-  *threads = k1_threads(kK1Lds[lc]);
-  *per_cu = kK1BlocksPerCU[lc];
-  switch (lc) {
-    case 0: return k1_fn_w<false, kK1Lds[0], true, k1_threads(kK1Lds[0])>(k.kw_words);
-    case 1: return k1_fn_w<false, kK1Lds[1], true, k1_threads(kK1Lds[1])>(k.kw_words);
-    default:
-      return k.rep ? k1_fn_w<false, kK1Lds[2], true, k1_threads(kK1Lds[2])>(k.kw_words)
-                   : k1_fn_w<false, kK1Lds[2], false, k1_threads(kK1Lds[2])>(k.kw_words);
-  }
+// the layout record of a table (test hooks): lc = k1_lds_class of its bytes
+static void k1_layout_fill(bool packed, size_t ns, size_t nc, size_t stride, size_t tab_bytes, int lc, K1LayoutView* o) {
+  o->packed = packed ? 1u : 0u;
+  o->states = (uint32_t)ns;
+  o->classes = (uint32_t)nc;
+  o->stride = (uint32_t)stride;
+  o->row_unit = (uint32_t)(stride * (packed ? 2 : 1));
+  o->table_bytes = (uint32_t)tab_bytes;
+  o->lds_class = (uint32_t)(lc >> 1);
+  o->rep = (uint32_t)(lc & 1);
+  o->lds_kib = packed ? (uint32_t)kK1PLdsK : o->lds_class <= 2 ? (uint32_t)kK1Lds[o->lds_class] : 0u;
+  const bool built = k1_has_kernel(packed, o->lds_class, o->rep);
+  o->threads = built ? (uint32_t)kK1Threads : 0u;
+  o->blocks_per_cu = built ? (uint32_t)kK1BlocksPerCU : 0u;
+}
+
+int k1_layout_of(uint32_t ns32, uint32_t nc32, K1LayoutView* out) {
+  *out = K1LayoutView{};
+  const size_t ns = ns32, nc = nc32;
+  if (!ns || !nc || nc > 128) return fail(TSG_ERR_ARG, "a keyword automaton has 1 to 128 classes and a state");
+  if (ns * nc > (1u << 24)) return fail(TSG_ERR_ARG, "keyword automaton exceeds LDS");
+  const size_t rs = k1_stride(nc, ns);
+  const bool packed = k1_packed_fits(ns, rs);
+  const size_t tab_bytes = (ns * rs + (ns * rs & 1)) * 2;  // k1_tables stages whole dwords
+  k1_layout_fill(packed, ns, nc, rs, tab_bytes, k1_lds_class(tab_bytes), out);
+  if ((ns - 1) * out->row_unit > 0xFFFF) return fail(TSG_ERR_ARG, "keyword automaton too large for 16-bit rows");
+  if (!packed && out->lds_class > 2) return fail(TSG_ERR_ARG, "keyword automaton exceeds LDS");
+  if (!out->threads) return fail(TSG_ERR_ARG, "no K1 kernel is built for the keyword automaton's layout");
+  return TSG_OK;
+}
+
+void device_rules_k1_layout(const DeviceRules* d, K1LayoutView* out) {
+  const DevK1& k = d->k1;
+  *out = K1LayoutView{};
+  k1_layout_fill(k.packed != 0, k.ns, (size_t)d->plan->kw_dfa->nclasses, k.nc, (size_t)k.tab_words * 4,
+                 (int)(k.lds_class * 2 + k.rep), out);
+  out->row_unit = k.row_unit;
+  out->kw_words = k.kw_words;
 }
 
 // a persistent grid of the resident blocks (each block stages the automaton once)
 static int launch_k1(DeviceRules* r, const K1Args& A, int64_t grid_cap, hipStream_t st) {
-  int threads = 0, per_cu = 0;
-  const void* fn = k1_fn(r->k1, &threads, &per_cu);
-  const uint64_t cap = (uint64_t)r->cus * per_cu;
+  const int threads = kK1Threads;
+  const void* fn = k1_fn(r->k1);
+  const uint64_t cap = (uint64_t)r->cus * kK1BlocksPerCU;
   const int grid = capped_grid(std::min<uint64_t>((A.nitems + threads - 1) / threads, cap), grid_cap);
   DevK1 d = r->k1;
   K1Args a = A;

@@ -1521,6 +1521,46 @@ int tsg_test_lane_buffers(tsg_ctx* c, tsg_lane_buffer* bufs, size_t bufs_cap, ui
   });
 }
 
+static void give_k1_layout(const K1LayoutView& v, tsg_k1_layout* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->packed = v.packed;
+  o->states = v.states;
+  o->classes = v.classes;
+  o->stride = v.stride;
+  o->row_unit = v.row_unit;
+  o->table_bytes = v.table_bytes;
+  o->lds_class = v.lds_class;
+  o->rep = v.rep;
+  o->lds_kib = v.lds_kib;
+  o->threads = v.threads;
+  o->blocks_per_cu = v.blocks_per_cu;
+  o->kw_words = v.kw_words;
+}
+
+int tsg_test_k1_layout_of(uint32_t states, uint32_t classes, tsg_k1_layout* out) {
+  if (!out) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    K1LayoutView v;
+    const int rc = k1_layout_of(states, classes, &v);
+    give_k1_layout(v, out);
+    return rc;
+  });
+}
+
+int tsg_test_k1_layout(tsg_ctx* c, tsg_k1_layout* out) {
+  if (!c || !out) return fail(TSG_ERR_ARG, "bad argument");
+  return guard([&]() -> int {
+    // (the context lock: no batch is enqueued, so no adaptation rebuilds the tables, meanwhile)
+    std::lock_guard<std::mutex> g(c->m);
+    if (c->emulate || !c->dr) return fail(TSG_ERR_ARG, "an emulated context has no device tables");
+    K1LayoutView v;
+    device_rules_k1_layout(c->dr, &v);
+    give_k1_layout(v, out);
+    out->k1_filter = device_rules_k1_filter(c->dr) ? 1u : 0u;
+    return TSG_OK;
+  });
+}
+
 int tsg_test_adaptation(tsg_ctx* c, tsg_adaptation_info* info, uint8_t* kw_unknown, size_t kw_unknown_len,
                         uint8_t* gate_open, size_t gate_open_len, uint8_t* event_everywhere,
                         size_t event_everywhere_len, uint32_t* hits, size_t hits_len, uint8_t* quiet, size_t quiet_len) {

@@ -509,6 +509,18 @@ def layout_reference(counts, nchunks, items_cap, max_dense=16):
                                 "dense_entries": int(tot[2]), "skipped": int(tot[3])}
 
 
+K1_LAYOUT_OF_KEYS = tuple(k for k, _ in N.K1Layout._fields_ if k not in ("kw_words", "k1_filter", "reserved"))
+
+
+def k1_layout_of(states, classes):
+    """tsg_test_k1_layout_of: the layout the automaton K1 gives a keyword automaton of
+    `states` x `classes` (Scanner.info()'s kw_states and kw_classes), as a dict of
+    tsg_k1_layout's fields.  Raises NativeError where no device tables can be made of it."""
+    v = N.K1Layout()
+    N.check(N.lib().tsg_test_k1_layout_of(int(states), int(classes), C.byref(v)))
+    return {k: int(getattr(v, k)) for k in K1_LAYOUT_OF_KEYS}
+
+
 def decode_results(buf, paths, rules):
     magic, nfiles = struct.unpack_from("<II", buf, 0)
     assert magic == 0x31475354 and nfiles == len(paths)
@@ -711,6 +723,14 @@ class GpuContext:
         lanes = [{bufs[k * n[1] + i].name.decode(): (int(bufs[k * n[1] + i].bytes), int(bufs[k * n[1] + i].allocs))
                   for i in range(n[1])} for k in range(n[0])]
         return lanes, (None if n[2] == 0xFFFFFFFF else int(n[2]))
+
+    def k1_layout(self):
+        """The layout of the context's automaton K1 (tsg_test_k1_layout): k1_layout_of's record
+        read from the device tables, with "kw_words" and "k1_filter" (1: batches under 4 GiB
+        run K1F, and the automaton only stands by)."""
+        v = N.K1Layout()
+        N.check(N.lib().tsg_test_k1_layout(self._h, C.byref(v)))
+        return {k: int(getattr(v, k)) for k, _ in N.K1Layout._fields_ if k != "reserved"}
 
     def k1_output(self, chunk):
         """(keyword bits [nfiles, kw_words], chunk event bits) of the last kernels() call."""
